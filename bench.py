@@ -8,7 +8,8 @@ A "step" is one data-parallel TRAIN step (forward + backward + gradient all-redu
 batch of synthetic clips resident in HBM: BASELINE.json cfg3/cfg4 -- per GPU 8 clips x 16 frames x 3x224x224,
 STE depth 6 / heads 8 / dim 512, KTD hidden 1024, bf16 compute with fp32 master weights and fp32
 residual stream.  Weak scaling: per-GPU batch fixed, value = (N * 8 clips) / max-over-ranks step time.
-Rank 0 prints ONE JSON line.  It also carries
+Rank 0 prints ONE JSON line.  A plain run sets up, warms up, times the K steps and prints the line, nothing more;
+--dump-outputs DIR also writes what the last timed step computed to DIR/*.npy.  With --full the line also carries
   roofline     : the step's dominant kernel family by time -- the bf16 NT GEMMs -- timed in situ with hipEvents on the
                  launch stream (maed_prof_*), summed over every instrumented launch, against the dense bf16 MFMA peak;
                  roofline_attention = the STE spatial-attention forward kernel north_star names (HBM roofline + MFMA
@@ -349,186 +350,38 @@ def parity_mode_line(dev, steps=5):
         maed_amd.set_float32_backward_precision(None)
 
 
-def main():
-    ap = argparse.ArgumentParser()
-    ap.add_argument("--gpus", type=int, default=1)
-    ap.add_argument("--steps", type=int, default=10)
-    ap.add_argument("--warmup", type=int, default=3)
-    ap.add_argument("--dtype", default="bf16", choices=["bf16", "f32"])
-    ap.add_argument("--f32-matmul", default=None, choices=["exact", "bf16x3", "bf16x6"],
-                    help="--dtype f32 only: engine of the fp32 matrix products (maed_amd.set_float32_matmul_precision); default: MAED_F32_MATMUL or exact")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-ddp-rehearsal", action="store_true", help="skip the one-rank rehearsal of the multi-GPU launch line (ddp.world1_forced_ms)")
-    ap.add_argument("--forward-only", action="store_true", help="cfg2: inference forward instead of the train step")
-    ap.add_argument("--workload", default="cfg3", choices=["cfg3", "cfg5"], help="cfg3 = BASELINE's metric workload (default); cfg5 = long-clip stress")
-    ap.add_argument("--graph-leg", action="store_true", help="(subprocess of the default run) the train step captured as one hipGraph: prints {\"graph\": ...}")
-    ap.add_argument("--no-graph-leg", action="store_true")
-    ap.add_argument("--simulate", action="store_true",
-                    help="TEST ONLY (tests/test_bench_world2.py): the whole driver -- process group, broadcast, bucketed all-reduce overlapped with backward, "
-                         "extra profiling steps, barriers, JSON -- on CPU tensors with the kernels on the host simulator and the gloo backend, tiny workload; "
-                         "the number it prints is meaningless")
-    ap.add_argument("--f32-backward", default=None, choices=["same", "bf16x1", "bf16"],
-                    help="--dtype f32 only: engine of the backward matrix products (maed_amd.set_float32_backward_precision): bf16x1 = one bf16 plane per operand")
-    ap.add_argument("--backbone-f32-matmul", default=None, choices=["bf16x3", "bf16x6"],
-                    help="--dtype f32 only: the backbone's own engine (MAED(backbone_f32_matmul=...)); default: the process-wide mode")
-    args = ap.parse_args()
-    if args.graph_leg:
-        return graph_leg_main(args)
-    # stdout carries ONE line, the JSON: native libraries print there too (RCCL writes a five-line version banner to stdout when a communicator is created), so
-    # file descriptor 1 points at stderr until the line is printed
-    sys.stdout.flush()
-    stdout_fd = os.dup(1)
-    os.dup2(2, 1)
+DUMP_MAX_ELEMS = 4 << 20      # per array; larger ones are written as a fixed seeded sample (the whole dump stays well under 64 MB)
 
-    if args.workload == "cfg5":   # BASELINE.json configs[4]: long-clip stress (per-GPU clips stated in config.workload)
-        CFG.update(clips=2, T=64, img=256, depth=12, heads=12, dim=768)
-    sim = args.simulate
-    if sim:                       # tiny model, host simulator, gloo: exercises the orchestration, not the kernels' speed
-        CFG.update(clips=1, T=2, img=32, depth=1, heads=2, dim=128, hidden=64)
-        sys.path.insert(0, os.path.join(ROOT, "tests"))
-        import _hostsim
-        sim_ctx = _hostsim.patched()
-        sim_ctx.__enter__()
-    world = int(os.environ.get("WORLD_SIZE", "1"))
-    rank = int(os.environ.get("RANK", "0"))
-    local_rank = int(os.environ.get("LOCAL_RANK", "0"))
-    # launched by torch.distributed.run (RANK / WORLD_SIZE / MASTER_* in the environment): one process per GPU over RCCL.  A 1-process
-    # launch under torchrun initialises the group too, and MAED_FORCE_COLLECTIVES=1 then issues every bucket's all-reduce anyway -- the
-    # whole multi-GPU code path (init, broadcast, bucketed RCCL all-reduce overlapped with backward, barrier) on a single GPU box.
-    force_coll = os.environ.get("MAED_FORCE_COLLECTIVES", "0") == "1"
-    if world > 1 or (force_coll and "RANK" in os.environ and "MASTER_PORT" in os.environ):
-        os.environ.setdefault("MASTER_ADDR", "127.0.0.1")
-        if sim:
-            dist.init_process_group("gloo")
-        else:
-            dist.init_process_group("nccl", device_id=torch.device("cuda", local_rank))
-    assert world == args.gpus, f"--gpus {args.gpus} but WORLD_SIZE={world}: launch with torch.distributed.run"
-    if not sim:
-        torch.cuda.set_device(local_rank)
-    dev = torch.device("cpu") if sim else torch.device("cuda", local_rank)
-    cuda_sync = (lambda: None) if sim else torch.cuda.synchronize
-    dtype = torch.bfloat16 if args.dtype == "bf16" else torch.float32
 
-    from maed_amd import _lib as L
-    from maed_amd.ddp import FusedAdam, GradBucketer, ParamArena
-    from maed_amd.loss import LossVideo
-    from maed_amd.resnetv2 import _ws_per_stage
-    lib = L.lib()  # raises if libmaed_hip.so is missing: no fallback
-    if args.f32_matmul:
-        import maed_amd
-        maed_amd.set_float32_matmul_precision(args.f32_matmul)
-    if args.f32_backward:
-        import maed_amd
-        maed_amd.set_float32_backward_precision(args.f32_backward)
+def dump_outputs(path, res, arena):
+    """--dump-outputs: what the last timed step handed its caller -- the model outputs, the objective and its terms, and (train step) the parameters as
+    Adam left them -- as float32 / float64 .npy files, so that two builds can be compared output for output on identical inputs"""
+    import numpy as np
+    loss, preds, terms = res
+    arrays = {k: v for k, v in preds.items() if torch.is_tensor(v)}
+    if loss is not None:
+        arrays["loss"] = loss
+        arrays.update({k: v for k, v in terms.items() if torch.is_tensor(v)})
+    if arena is not None:
+        arrays["params"] = arena.flat
+    os.makedirs(path, exist_ok=True)
+    total = 0
+    for name, t in sorted(arrays.items()):
+        t = t.detach()
+        if t.numel() > DUMP_MAX_ELEMS:   # same elements on every run: sorted indices from a fixed seed
+            idx = torch.randint(0, t.numel(), (DUMP_MAX_ELEMS,), generator=torch.Generator().manual_seed(0)).sort().values
+            t, name = t.reshape(-1)[idx.to(t.device)], name + "_sample"
+        a = (t.double() if t.dtype == torch.float64 else t.float()).cpu().numpy()
+        np.save(os.path.join(path, name + ".npy"), a)
+        total += a.nbytes
+    assert total <= 64 << 20, f"--dump-outputs wrote {total / 2 ** 20:.1f} MB"
+    log(f"dumped {len(arrays)} arrays ({total / 2 ** 20:.1f} MB) to {path}")
 
-    log(f"building model ({args.dtype}) on {dev}")
-    model = _SimModel() if sim else build_model(dtype, dev, args.backbone_f32_matmul)
-    gen = torch.Generator().manual_seed(1000 + rank)
-    clip = torch.randn(CFG["clips"], CFG["T"], 3, CFG["img"], CFG["img"], generator=gen).to(dev)
-    tgt = make_targets(CFG["clips"], CFG["T"], dev, gen)
 
-    if args.forward_only:
-        model.eval()
-
-        def step():
-            with torch.no_grad():
-                model(clip)
-    else:
-        model.train()
-        arena = ParamArena(model)
-        comm = None
-        # transport of the gradient all-reduce (train.py:113,182): round 4 -- the LIBRARY's communicator (maed_comm_*: RCCL bound by dlsym, own side stream, event fences)
-        # is the default whenever collectives run (a process group with more than one rank, or forced ones); MAED_COMM=torch selects torch.distributed's
-        # ProcessGroupNCCL (the same RCCL).  If the own communicator cannot be created on this box the run falls back to torch.distributed, says so on stderr and in
-        # the JSON line (ddp.transport) -- a scaling run must not die of a transport choice.
-        want_direct = os.environ.get("MAED_COMM", "direct") == "direct" and not sim and dist.is_available() and dist.is_initialized() and (world > 1 or force_coll)
-        if want_direct:
-            from maed_amd.ddp import RcclComm
-            # agree on feasibility with a NON-collective step first (load + symbol check on every rank, then one all-reduce of the verdict): creating the communicator
-            # is itself collective, so a rank that cannot must say so before anybody enters the constructor -- otherwise its peers hang in ncclCommInitRank (ADVICE r4)
-            ok_here, why = RcclComm.available()
-            if not ok_here:
-                log(f"MAED_COMM=direct: own RCCL communicator unavailable on rank {rank} ({why}); every rank falls back to torch.distributed")
-            ok = torch.tensor([1.0 if ok_here else 0.0], device=dev)
-            dist.all_reduce(ok, op=dist.ReduceOp.MIN)
-            if ok.item() == 1.0:
-                # every rank can bind the library: the collective constructor.  A failure in here (ncclCommInitRank) is, in practice, the same on every rank -- agree
-                # once more and fall back together rather than lose the run; a rank-local failure is what the non-collective check above was for
-                try:
-                    comm = RcclComm()
-                except Exception as e:  # noqa: BLE001
-                    log(f"MAED_COMM=direct: communicator creation failed on rank {rank} ({e}); falling back to torch.distributed")
-                    comm = None
-                ok2 = torch.tensor([1.0 if comm is not None else 0.0], device=dev)
-                dist.all_reduce(ok2, op=dist.ReduceOp.MIN)
-                if ok2.item() == 0.0 and comm is not None:
-                    comm.destroy()
-                    comm = None
-        bucketer = GradBucketer(arena, model, comm=comm, force_collectives=force_coll, **(dict(bucket_bytes=16 << 10) if sim else {}))
-        bucketer.broadcast_parameters(0)
-        opt = FusedAdam(arena, lr=1e-4, weight_decay=1e-5, bucketer=bucketer)  # configs/config_stage2.yaml:63-66
-        criterion = LossVideo(**LOSS_W)                                        # lib/core/loss.py via maed_loss_fwd_bwd
-
-        def step():
-            opt.zero_grad()
-            loss, _ = criterion(model(clip), tgt, None)
-            loss.backward()
-            opt.step()
-            return loss
-
-    def fence():
-        cuda_sync()
-        if dist.is_available() and dist.is_initialized():
-            dist.barrier()
-        cuda_sync()
-
-    # setup, not a benchmark step: the first pass through the model makes MIOpen search its convolution algorithms (~20 s) and
-    # loads every code object; it is kept out of the W warm-up steps so that a small --warmup cannot put it next to the timed region
-    t1 = time.perf_counter()
-    first_loss = step()
-    cuda_sync()
-    # the objective of the very first step (seeded parameters, seeded batch, before any update): equal -- to the order of fp32 atomics -- whatever the launch line,
-    # the transport of the gradient all-reduce or the number of ranks' worth of machinery around it (tests/test_gpu_model.py compares the two launch lines)
-    first_loss = None if first_loss is None else float(first_loss.detach().float().item())
-    log(f"setup pass (MIOpen algorithm search, code-object loading): {time.perf_counter() - t1:.3f}s")
-    for i in range(args.warmup):
-        t1 = time.perf_counter()
-        step()
-        cuda_sync()
-        log(f"warm-up step {i}: {time.perf_counter() - t1:.3f}s")
-    fence()
-    # the contract's number: K steps bracketed by barrier + synchronize; beside it one event per step boundary on the launch stream
-    # (every kernel of a step is enqueued on torch's current stream) for the per-step median / p10 / p90 (SURVEY 8(d))
-    class _HostMark:       # --simulate: host clock in place of hipEvents
-        def record(self):
-            self.t = time.perf_counter()
-
-        def elapsed_time(self, other):
-            return 1e3 * (other.t - self.t)
-    marks = [(_HostMark() if sim else torch.cuda.Event(enable_timing=True)) for _ in range(args.steps + 1)]
-    dev_allocs0 = 0 if sim else torch.cuda.memory_stats(dev).get("num_device_alloc", 0)     # hipMalloc calls of the caching allocator so far
-    t0 = time.perf_counter()
-    marks[0].record()
-    for i in range(args.steps):
-        step()
-        marks[i + 1].record()
-    fence()
-    dt = time.perf_counter() - t0
-    dev_allocs = 0 if sim else torch.cuda.memory_stats(dev).get("num_device_alloc", 0) - dev_allocs0
-    in_order = [marks[i].elapsed_time(marks[i + 1]) for i in range(args.steps)]
-    log("per-step ms (hipEvents, in order): " + " ".join(f"{t:.1f}" for t in in_order))
-    per_step = sorted(in_order)
-    pct = lambda q: per_step[min(len(per_step) - 1, max(0, int(round(q * (len(per_step) - 1)))))]
-    step_stats = dict(median_ms=round(pct(0.5), 3), p10_ms=round(pct(0.1), 3), p90_ms=round(pct(0.9), 3), min_ms=round(per_step[0], 3),
-                      max_ms=round(per_step[-1], 3), how="hipEvent per step boundary on the launch stream, this rank",
-                      device_allocations_in_timed_region=dev_allocs)     # > 0: the caching allocator was still growing (hipMalloc inside the timed steps: more --warmup)
-    tt = torch.tensor([dt], device=dev, dtype=torch.float64)
-    if world > 1:
-        dist.all_reduce(tt, op=dist.ReduceOp.MAX)
-    dt = tt.item()
-    ms_per_step = 1e3 * dt / args.steps
-    log(f"timed {args.steps} steps: {ms_per_step:.2f} ms/step")
-
+def full_legs(args, step, fence, lib, dev, dtype, rank, world, sim):
+    """--full only: what the benchmark measures beyond its headline figure, after the timed steps -- the host's enqueue time per step, in-situ kernel timing for
+    the rooflines (extra steps every rank takes part in), and on a single rank the CPU baseline, the fp32-accurate mode's line and the parity probe.  Returns the
+    fields it adds to the JSON line."""
     # ---- host enqueue time of one step (extra steps, untimed region): the wall time step() takes to RETURN when the GPU queue is empty, i.e. what the host
     # needs to issue a step's ~700 launches; the step is GPU-bound as long as this stays below ms_per_step
     host_ms = []
@@ -698,6 +551,237 @@ def main():
         except Exception as e:
             cpu["parity_probe"] = dict(rel_err=None, note=f"failed: {e!r}")
 
+    return dict(host_enqueue_ms=host_enqueue_ms, roofline=roofline, roofline_nt=roofline_nt, roofline_attention=roofline_attention, roofline_wgrad=roofline_wgrad,
+                kernels=kernels, kernel_groups=groups, cpu=cpu)
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--gpus", type=int, default=1)
+    ap.add_argument("--steps", type=int, default=10)
+    ap.add_argument("--warmup", type=int, default=3)
+    ap.add_argument("--dtype", default="bf16", choices=["bf16", "f32"])
+    ap.add_argument("--f32-matmul", default=None, choices=["exact", "bf16x3", "bf16x6"],
+                    help="--dtype f32 only: engine of the fp32 matrix products (maed_amd.set_float32_matmul_precision); default: MAED_F32_MATMUL or exact")
+    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--no-ddp-rehearsal", action="store_true", help="skip the one-rank rehearsal of the multi-GPU launch line (ddp.world1_forced_ms)")
+    ap.add_argument("--forward-only", action="store_true", help="cfg2: inference forward instead of the train step")
+    ap.add_argument("--workload", default="cfg3", choices=["cfg3", "cfg5"], help="cfg3 = BASELINE's metric workload (default); cfg5 = long-clip stress")
+    ap.add_argument("--graph-leg", action="store_true", help="(subprocess of the default run) the train step captured as one hipGraph: prints {\"graph\": ...}")
+    ap.add_argument("--no-graph-leg", action="store_true")
+    ap.add_argument("--simulate", action="store_true",
+                    help="TEST ONLY (tests/test_bench_world2.py): the whole driver -- process group, broadcast, bucketed all-reduce overlapped with backward, "
+                         "extra profiling steps (--full), barriers, JSON -- on CPU tensors with the kernels on the host simulator and the gloo backend, tiny workload; "
+                         "the number it prints is meaningless")
+    ap.add_argument("--f32-backward", default=None, choices=["same", "bf16x1", "bf16"],
+                    help="--dtype f32 only: engine of the backward matrix products (maed_amd.set_float32_backward_precision): bf16x1 = one bf16 plane per operand")
+    ap.add_argument("--backbone-f32-matmul", default=None, choices=["bf16x3", "bf16x6"],
+                    help="--dtype f32 only: the backbone's own engine (MAED(backbone_f32_matmul=...)); default: the process-wide mode")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps, everything beyond the headline figure: host enqueue time, in-situ kernel timing and rooflines, and on one rank the "
+                         "CPU baseline, the fp32-accurate mode, the parity probe, the one-rank DDP rehearsal and the hipGraph leg (each --no-* flag drops its part)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step computed to DIR/<name>.npy (float32 / float64): the model outputs, the loss and its terms, "
+                         "and the updated parameters (a fixed seeded sample of them).  That step starts from the seeded initial state (restored "
+                         "before it, outside the timing), so two runs with the same arguments compute the same outputs up to one step's rounding")
+    args = ap.parse_args()
+    if args.graph_leg:
+        return graph_leg_main(args)
+    # stdout carries ONE line, the JSON: native libraries print there too (RCCL writes a five-line version banner to stdout when a communicator is created), so
+    # file descriptor 1 points at stderr until the line is printed
+    sys.stdout.flush()
+    stdout_fd = os.dup(1)
+    os.dup2(2, 1)
+
+    if args.workload == "cfg5":   # BASELINE.json configs[4]: long-clip stress (per-GPU clips stated in config.workload)
+        CFG.update(clips=2, T=64, img=256, depth=12, heads=12, dim=768)
+    sim = args.simulate
+    if sim:                       # tiny model, host simulator, gloo: exercises the orchestration, not the kernels' speed
+        CFG.update(clips=1, T=2, img=32, depth=1, heads=2, dim=128, hidden=64)
+        sys.path.insert(0, os.path.join(ROOT, "tests"))
+        import _hostsim
+        sim_ctx = _hostsim.patched()
+        sim_ctx.__enter__()
+    world = int(os.environ.get("WORLD_SIZE", "1"))
+    rank = int(os.environ.get("RANK", "0"))
+    local_rank = int(os.environ.get("LOCAL_RANK", "0"))
+    # launched by torch.distributed.run (RANK / WORLD_SIZE / MASTER_* in the environment): one process per GPU over RCCL.  A 1-process
+    # launch under torchrun initialises the group too, and MAED_FORCE_COLLECTIVES=1 then issues every bucket's all-reduce anyway -- the
+    # whole multi-GPU code path (init, broadcast, bucketed RCCL all-reduce overlapped with backward, barrier) on a single GPU box.
+    force_coll = os.environ.get("MAED_FORCE_COLLECTIVES", "0") == "1"
+    if world > 1 or (force_coll and "RANK" in os.environ and "MASTER_PORT" in os.environ):
+        os.environ.setdefault("MASTER_ADDR", "127.0.0.1")
+        if sim:
+            dist.init_process_group("gloo")
+        else:
+            dist.init_process_group("nccl", device_id=torch.device("cuda", local_rank))
+    assert world == args.gpus, f"--gpus {args.gpus} but WORLD_SIZE={world}: launch with torch.distributed.run"
+    if not sim:
+        torch.cuda.set_device(local_rank)
+    dev = torch.device("cpu") if sim else torch.device("cuda", local_rank)
+    cuda_sync = (lambda: None) if sim else torch.cuda.synchronize
+    dtype = torch.bfloat16 if args.dtype == "bf16" else torch.float32
+
+    from maed_amd import _lib as L
+    from maed_amd.ddp import FusedAdam, GradBucketer, ParamArena
+    from maed_amd.loss import LossVideo
+    from maed_amd.resnetv2 import _ws_per_stage
+    lib = L.lib()  # raises if libmaed_hip.so is missing: no fallback
+    if args.f32_matmul:
+        import maed_amd
+        maed_amd.set_float32_matmul_precision(args.f32_matmul)
+    if args.f32_backward:
+        import maed_amd
+        maed_amd.set_float32_backward_precision(args.f32_backward)
+
+    log(f"building model ({args.dtype}) on {dev}")
+    if sim:
+        torch.manual_seed(0)      # (build_model seeds the real model the same way: same arguments, same inputs)
+    model = _SimModel() if sim else build_model(dtype, dev, args.backbone_f32_matmul)
+    gen = torch.Generator().manual_seed(1000 + rank)
+    clip = torch.randn(CFG["clips"], CFG["T"], 3, CFG["img"], CFG["img"], generator=gen).to(dev)
+    tgt = make_targets(CFG["clips"], CFG["T"], dev, gen)
+
+    if args.forward_only:
+        model.eval()
+
+        def step():
+            with torch.no_grad():
+                return None, model(clip), {}
+    else:
+        model.train()
+        arena = ParamArena(model)
+        comm = None
+        # transport of the gradient all-reduce (train.py:113,182): round 4 -- the LIBRARY's communicator (maed_comm_*: RCCL bound by dlsym, own side stream, event fences)
+        # is the default whenever collectives run (a process group with more than one rank, or forced ones); MAED_COMM=torch selects torch.distributed's
+        # ProcessGroupNCCL (the same RCCL).  If the own communicator cannot be created on this box the run falls back to torch.distributed, says so on stderr and in
+        # the JSON line (ddp.transport) -- a scaling run must not die of a transport choice.
+        want_direct = os.environ.get("MAED_COMM", "direct") == "direct" and not sim and dist.is_available() and dist.is_initialized() and (world > 1 or force_coll)
+        if want_direct:
+            from maed_amd.ddp import RcclComm
+            # agree on feasibility with a NON-collective step first (load + symbol check on every rank, then one all-reduce of the verdict): creating the communicator
+            # is itself collective, so a rank that cannot must say so before anybody enters the constructor -- otherwise its peers hang in ncclCommInitRank (ADVICE r4)
+            ok_here, why = RcclComm.available()
+            if not ok_here:
+                log(f"MAED_COMM=direct: own RCCL communicator unavailable on rank {rank} ({why}); every rank falls back to torch.distributed")
+            ok = torch.tensor([1.0 if ok_here else 0.0], device=dev)
+            dist.all_reduce(ok, op=dist.ReduceOp.MIN)
+            if ok.item() == 1.0:
+                # every rank can bind the library: the collective constructor.  A failure in here (ncclCommInitRank) is, in practice, the same on every rank -- agree
+                # once more and fall back together rather than lose the run; a rank-local failure is what the non-collective check above was for
+                try:
+                    comm = RcclComm()
+                except Exception as e:  # noqa: BLE001
+                    log(f"MAED_COMM=direct: communicator creation failed on rank {rank} ({e}); falling back to torch.distributed")
+                    comm = None
+                ok2 = torch.tensor([1.0 if comm is not None else 0.0], device=dev)
+                dist.all_reduce(ok2, op=dist.ReduceOp.MIN)
+                if ok2.item() == 0.0 and comm is not None:
+                    comm.destroy()
+                    comm = None
+        bucketer = GradBucketer(arena, model, comm=comm, force_collectives=force_coll, **(dict(bucket_bytes=16 << 10) if sim else {}))
+        bucketer.broadcast_parameters(0)
+        opt = FusedAdam(arena, lr=1e-4, weight_decay=1e-5, bucketer=bucketer)  # configs/config_stage2.yaml:63-66
+        criterion = LossVideo(**LOSS_W)                                        # lib/core/loss.py via maed_loss_fwd_bwd
+
+        def step():
+            opt.zero_grad()
+            preds = model(clip)
+            loss, terms = criterion(preds, tgt, None)
+            loss.backward()
+            opt.step()
+            return loss, preds, terms
+
+    def fence():
+        cuda_sync()
+        if dist.is_available() and dist.is_initialized():
+            dist.barrier()
+        cuda_sync()
+
+    # --dump-outputs (train step): the seeded state before the first step -- parameters, Adam's (zero) moments and step count, the generators' positions.
+    # The last timed step starts again from it: the fp32 atomics of the weight gradients round differently from run to run, and over the many updates before
+    # the last step that rounding would grow into different parameters; from the seeded state, two runs differ by one step's rounding at most
+    snapshot = None
+    if args.dump_outputs and not args.forward_only:
+        snapshot = (arena.flat.clone(), torch.get_rng_state(), None if sim else torch.cuda.get_rng_state(dev))
+
+    def restore():
+        flat, cpu_rng, dev_rng = snapshot
+        arena.flat.copy_(flat)
+        opt.exp_avg.zero_()
+        opt.exp_avg_sq.zero_()
+        opt.step_count = 0
+        torch.set_rng_state(cpu_rng)
+        if dev_rng is not None:
+            torch.cuda.set_rng_state(dev_rng, dev)
+        from maed_amd import ops as _ops
+        _ops.bump_weight_epoch()        # the parameters changed in place: the modules refresh their compute-dtype weight copies
+
+    # setup, not a benchmark step: the first pass through the model makes MIOpen search its convolution algorithms (~20 s) and
+    # loads every code object; it is kept out of the W warm-up steps so that a small --warmup cannot put it next to the timed region
+    t1 = time.perf_counter()
+    first_loss = step()[0]
+    cuda_sync()
+    # the objective of the very first step (seeded parameters, seeded batch, before any update): equal -- to the order of fp32 atomics -- whatever the launch line,
+    # the transport of the gradient all-reduce or the number of ranks' worth of machinery around it (tests/test_gpu_model.py compares the two launch lines)
+    first_loss = None if first_loss is None else float(first_loss.detach().float().item())
+    log(f"setup pass (MIOpen algorithm search, code-object loading): {time.perf_counter() - t1:.3f}s")
+    for i in range(args.warmup):
+        t1 = time.perf_counter()
+        step()
+        cuda_sync()
+        log(f"warm-up step {i}: {time.perf_counter() - t1:.3f}s")
+    fence()
+    # the contract's number: K steps bracketed by barrier + synchronize; beside it one event per step boundary on the launch stream
+    # (every kernel of a step is enqueued on torch's current stream) for the per-step median / p10 / p90 (SURVEY 8(d))
+    class _HostMark:       # --simulate: host clock in place of hipEvents
+        def record(self):
+            self.t = time.perf_counter()
+
+        def elapsed_time(self, other):
+            return 1e3 * (other.t - self.t)
+    marks = [(_HostMark() if sim else torch.cuda.Event(enable_timing=True)) for _ in range(args.steps + 1)]
+    paused = [(_HostMark() if sim else torch.cuda.Event(enable_timing=True)) for _ in range(2)]      # brackets restore() on the launch stream
+    dev_allocs0 = 0 if sim else torch.cuda.memory_stats(dev).get("num_device_alloc", 0)     # hipMalloc calls of the caching allocator so far
+    t0 = time.perf_counter()
+    marks[0].record()
+    for i in range(args.steps):
+        if snapshot is not None and i == args.steps - 1:
+            paused[0].record()
+            restore()
+            paused[1].record()
+        res = step()
+        if i < args.steps - 1:
+            res = None          # only the last step's results outlive their step
+        marks[i + 1].record()
+    fence()
+    dt = time.perf_counter() - t0
+    dev_allocs = 0 if sim else torch.cuda.memory_stats(dev).get("num_device_alloc", 0) - dev_allocs0
+    in_order = [marks[i].elapsed_time(marks[i + 1]) for i in range(args.steps)]
+    if snapshot is not None:            # restore() is no part of a step: its time on the launch stream comes off the last step and the total
+        restore_ms = paused[0].elapsed_time(paused[1])
+        in_order[-1] -= restore_ms
+        dt -= restore_ms / 1e3
+        log(f"restore before the last timed step: {restore_ms:.3f} ms (not counted)")
+        snapshot = None
+    log("per-step ms (hipEvents, in order): " + " ".join(f"{t:.1f}" for t in in_order))
+    per_step = sorted(in_order)
+    pct = lambda q: per_step[min(len(per_step) - 1, max(0, int(round(q * (len(per_step) - 1)))))]
+    step_stats = dict(median_ms=round(pct(0.5), 3), p10_ms=round(pct(0.1), 3), p90_ms=round(pct(0.9), 3), min_ms=round(per_step[0], 3),
+                      max_ms=round(per_step[-1], 3), how="hipEvent per step boundary on the launch stream, this rank",
+                      device_allocations_in_timed_region=dev_allocs)     # > 0: the caching allocator was still growing (hipMalloc inside the timed steps: more --warmup)
+    tt = torch.tensor([dt], device=dev, dtype=torch.float64)
+    if world > 1:
+        dist.all_reduce(tt, op=dist.ReduceOp.MAX)
+    dt = tt.item()
+    ms_per_step = 1e3 * dt / args.steps
+    log(f"timed {args.steps} steps: {ms_per_step:.2f} ms/step")
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, res, None if args.forward_only else arena)
+    res = None
+    extra = full_legs(args, step, fence, lib, dev, dtype, rank, world, sim) if args.full else {}
+    cpu = extra.pop("cpu", None)
+
     if rank == 0:
         clips = CFG["clips"] * world
         out = {
@@ -714,29 +798,31 @@ def main():
                        "smpl": "synthetic SMPL-shaped parameters (licensed model file unavailable)",
                        "input": "one synthetic clip batch resident in HBM, reused by every step: no host-to-device copy in the timed region (DESIGN.md section 5: a 77 MB fp32 "
                                 "batch is ~1.4 ms over PCIe Gen5 when not overlapped)"},
-            "step_time": step_stats, "host_enqueue_ms": host_enqueue_ms, "first_step_loss": first_loss,
+            "step_time": step_stats, "first_step_loss": first_loss,
             # data-parallel diagnostics (N > 1 or forced collectives): transport, ranks, gradient buckets and when each was launched in the last backward
             "ddp": (None if args.forward_only else dict(transport="maed_comm (own RCCL communicator)" if comm is not None else ("torch.distributed/" + (dist.get_backend() if dist.is_initialized() else "none")),
                                                      rccl_ranks=world, collectives=bool(bucketer.collectives), gradient_dtype="f32",
                                                      buckets=[dict(mbytes=round(4 * (e - s) / 2 ** 20, 2), params=n) for s, e, n in bucketer.buckets],
                                                      bucket_launch_order=list(bucketer.launch_order), per_stage_weight_std=bool(_ws_per_stage()))),
-            "roofline": roofline, "roofline_nt": roofline_nt, "roofline_attention": roofline_attention, "roofline_wgrad": roofline_wgrad, "kernels": kernels,
-            "kernel_groups": groups,
-            "cpu_baseline": cpu,
-            "parity_err_bf16": (cpu or {}).get("parity_probe", {}).get("rel_err", {}).get("bf16") if cpu and (cpu.get("parity_probe") or {}).get("rel_err") else None,
-            "parity_mode": (cpu or {}).pop("parity_mode", None) if cpu else None,
         }
-        if world == 1 and not sim and not args.forward_only and not args.no_ddp_rehearsal and not args.no_cpu_baseline and args.dtype == "bf16" and args.workload == "cfg3" and out.get("ddp") is not None:
+        if args.full:
+            out.update(extra)
+            out.update({
+                "cpu_baseline": cpu,
+                "parity_err_bf16": (cpu or {}).get("parity_probe", {}).get("rel_err", {}).get("bf16") if cpu and (cpu.get("parity_probe") or {}).get("rel_err") else None,
+                "parity_mode": (cpu or {}).pop("parity_mode", None) if cpu else None,
+            })
+        if args.full and world == 1 and not sim and not args.forward_only and not args.no_ddp_rehearsal and not args.no_cpu_baseline and args.dtype == "bf16" and args.workload == "cfg3" and out.get("ddp") is not None:
             out["ddp"]["rehearsal"] = ddp_rehearsal(ms_per_step)
-        if world == 1 and not sim and not args.forward_only and not args.no_graph_leg and not args.no_cpu_baseline and args.dtype == "bf16" and args.workload == "cfg3":
+        if args.full and world == 1 and not sim and not args.forward_only and not args.no_graph_leg and not args.no_cpu_baseline and args.dtype == "bf16" and args.workload == "cfg3":
             out["graph"] = graph_leg()      # the same step replayed as one hipGraph (host time per step)
         # first-class beside `value`: the same train step in the fastest mode whose OUTPUTS meet north_star's 1e-3 on SMPL parameters at full module
         # size -- `value` itself is the bf16 mode's number, at bf16 accuracy
-        pm = out.get("parity_mode") or {}
-        fw = pm.get("fastest_within_1e3")
-        out["value_at_1e3"] = (dict(value=fw["clips_per_sec"], unit="video-clips/sec", ms_per_step=fw["ms_per_step"], theta_rel_err=fw["theta_rel_err"], mode=fw["name"],
-                                    note="fp32 forward operands, split-bf16 matrix products (3 MFMAs); variant bf16x3_fwd_bf16_twin_bwd: the backward is the bf16 mode's, on bf16 "
-                                         "twins of what the forward saved (DESIGN.md section 4); see parity_mode.variants") if fw else None)
+        if args.full:
+            fw = (out.get("parity_mode") or {}).get("fastest_within_1e3")
+            out["value_at_1e3"] = (dict(value=fw["clips_per_sec"], unit="video-clips/sec", ms_per_step=fw["ms_per_step"], theta_rel_err=fw["theta_rel_err"], mode=fw["name"],
+                                        note="fp32 forward operands, split-bf16 matrix products (3 MFMAs); variant bf16x3_fwd_bf16_twin_bwd: the backward is the bf16 mode's, on bf16 "
+                                             "twins of what the forward saved (DESIGN.md section 4); see parity_mode.variants") if fw else None)
         sys.stdout.flush()
         os.dup2(stdout_fd, 1)
         print(json.dumps(out), flush=True)

@@ -17,7 +17,8 @@ def test_bench_main_two_ranks_gloo_simulator():
     port = 29700 + os.getpid() % 200
     env = dict(os.environ, MAED_SYNTHETIC_SMPL_OK="1", OMP_NUM_THREADS="2")
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2", "--master-addr", "127.0.0.1", "--master-port", str(port),
-           os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "2", "--warmup", "1", "--simulate", "--dtype", "f32", "--no-cpu-baseline"]
+           os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "2", "--warmup", "1", "--simulate", "--dtype", "f32", "--no-cpu-baseline",
+           "--full"]
     out = subprocess.run(cmd, capture_output=True, text=True, timeout=240, env=env, cwd=ROOT)
     assert out.returncode == 0, out.stderr[-3000:]
     lines = [l for l in out.stdout.splitlines() if l.startswith("{")]
@@ -31,3 +32,4 @@ def test_bench_main_two_ranks_gloo_simulator():
     assert ddp["rccl_ranks"] == 2 and ddp["collectives"] is True and ddp["transport"].startswith("torch.distributed/gloo")
     assert len(ddp["buckets"]) >= 1 and sorted(ddp["bucket_launch_order"]) == list(range(len(ddp["buckets"])))
     assert ddp["per_stage_weight_std"] is True
+    assert d["host_enqueue_ms"] > 0 and "kernels" in d                # --full: the extra steps after the timed ones ran on both ranks
