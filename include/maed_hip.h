@@ -616,6 +616,27 @@ int maed_eval_accel(const float* joints, const float* joints_gt, int N, int J, f
 /* out[n] = mean_v ||pred_verts[n,v] - target_verts[n,v]||, (N,V,3) each (eval_utils.py:88-90 compute_error_verts). */
 int maed_eval_vertex_error(const float* pred_verts, const float* target_verts, int N, int V, float* out, void* stream);
 
+/* ---- clip preprocessing on the device (csrc/preprocess.hip) --------------------------------------------------------
+ * The reference's transform chain (train.py:41-70; lib/data_utils/transforms/crop.py:88-92, color_jitter.py:55-97, random_erase.py:23-87,
+ * random_hflip.py:98-121, basic.py:24-49, 95-108) from uint8 source pixels to the normalised fp32 tensor out (F, 3, H, W) = (N, T, 3, H, W).
+ *   src         packed uint8 buffer of src_bytes (< 2^31) bytes holding one RGB (HWC) region per frame
+ *   frame_i     int32 (F, 8): byte offset of the region in src, region height, width, row pitch in bytes, clip index (0..N-1),
+ *               rows erased at the top, rows erased at the bottom, 0
+ *   frame_minv  fp32 (F, 6): the 2 x 3 map from patch pixel (x, y) to REGION coordinates (the inverse of crop.py's `trans`, shifted to the region's origin)
+ *   clip_i      int32 (N, 8): flip flag, four operation codes in the order drawn (0 none, 1 brightness, 2 saturation, 3 hue, 4 contrast),
+ *               the hue shift in levels (0..255, added to H modulo 256), 0, 0
+ *   clip_f      fp32 (N, 4): brightness, saturation, (unused), contrast factor
+ *   norm_host   HOST pointer to 6 floats: mean r, g, b, std r, g, b
+ *   has_contrast  non-zero if any clip lists operation 4 (the caller built the tables and knows; the library does not read them back)
+ *   form        0 = direct if has_contrast is 0, else two launches; 1 = direct (one launch, nothing staged; has_contrast must be 0); 2 = one workgroup per
+ *               frame with the uint8 patch in LDS (3*H*W bytes must fit; DIAGNOSTIC: measured 2-3x slower than 1 / 3, never chosen by 0, kept as a bit-identical cross-check); 3 = two launches through `workspace`.  All forms give the same bits.
+ *   workspace   form 3 (and form 0 where it resolves to 3): maed_clip_preprocess_workspace(F, H, W) bytes, 16-byte aligned; else may be NULL
+ * W % 4 == 0, F <= 65535.  Sampling is bilinear with zeros outside the region, rounded to nearest; every jitter operation maps uint8 to uint8. */
+size_t maed_clip_preprocess_workspace(int F, int H, int W);
+int maed_clip_preprocess(const uint8_t* src, int64_t src_bytes, const int32_t* frame_i, const float* frame_minv, const int32_t* clip_i,
+                         const float* clip_f, int F, int N, int H, int W, const float* norm_host, int has_contrast, int form, float* out,
+                         void* workspace, size_t workspace_bytes, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -1480,3 +1480,32 @@ class Conv3x3Fn(torch.autograd.Function):
             if need_x and not own_dx:
                 dx = gx if sym else gx[:, :, ph // 2:ph // 2 + H, pw // 2:pw // 2 + W]
         return dx, dw, None, None, None, None, None
+
+
+# ----------------------------------------------------------------------------------------------
+# clip preprocessing (csrc/preprocess.hip; the host side lives in maed_amd/data.py)
+# ----------------------------------------------------------------------------------------------
+PRE_FORM_AUTO, PRE_FORM_DIRECT, PRE_FORM_LDS, PRE_FORM_TWO = range(4)
+
+
+def clip_preprocess_workspace(F, H, W):
+    return int(L.lib().maed_clip_preprocess_workspace(F, H, W))
+
+
+def clip_preprocess(blob, offsets, src_bytes, F, N, H, W, mean, std, has_contrast, out, form=PRE_FORM_AUTO):
+    """maed_clip_preprocess on ONE uint8 device buffer that holds the four parameter tables and the packed source pixels (data.pack_clips lays it out,
+    data.preprocess_clips uploads it: the per-step tables travel beside the pixels, not through the content-keyed _TABLES cache, whose live entries
+    they would evict).  offsets = byte offsets of (frame_i, frame_minv, clip_i, clip_f, pixels) in blob.  out: fp32 (F, 3, H, W), contiguous."""
+    base = _p(blob)
+    _p(out)
+    if out.dtype != torch.float32 or not out.is_contiguous() or out.numel() != F * 3 * H * W:
+        raise L.MaedHipError(f"clip_preprocess: out must be contiguous fp32 with {F * 3 * H * W} elements")
+    if blob.dtype != torch.uint8 or offsets[4] + src_bytes > blob.numel():
+        raise L.MaedHipError("clip_preprocess: the packed buffer is shorter than its tables say")
+    need = clip_preprocess_workspace(F, H, W) if (form == PRE_FORM_TWO or (form == PRE_FORM_AUTO and has_contrast)) else 0
+    ws = _scratch(need, out.device, tag="clip_preprocess") if need else None
+    norm = (C.c_float * 6)(*[float(v) for v in mean], *[float(v) for v in std])
+    fi, fm, ci, cf, px = (base + o for o in offsets)
+    check(L.lib().maed_clip_preprocess(px, src_bytes, fi, fm, ci, cf, F, N, H, W, norm, int(bool(has_contrast)), form, _p(out), _p(ws), need, _stream()),
+          "clip_preprocess")
+    return out
