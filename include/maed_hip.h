@@ -637,6 +637,36 @@ int maed_clip_preprocess(const uint8_t* src, int64_t src_bytes, const int32_t* f
                          const float* clip_f, int F, int N, int H, int W, const float* norm_host, int has_contrast, int form, float* out,
                          void* workspace, size_t workspace_bytes, void* stream);
 
+/* ---- mesh overlay on the device (csrc/render.hip; definitions in docs/design/11_render.md) ---------------------------------------------
+ * The reference's lib/utils/renderer.py Renderer.render (pyrender on OpenGL) as a compute rasteriser: B meshes that share one face list are rotated by 180 degrees
+ * about x (renderer.py:78-79), optionally rotated again (:84-86), projected by the weak-perspective camera (:31-38), z-buffered, shaded and written over uint8 frames.
+ *   verts       fp32 (B, V, 3)
+ *   faces       DEVICE int32 (n_faces, 3); every index is range-checked in the kernels as well (a face with an index outside [0, V) is never gathered)
+ *   faces_host  HOST copy of faces, or NULL: when given, an index outside [0, V) fails the call with MAED_ERR_ARG before anything is launched
+ *   vf_off, vf_idx  DEVICE int32 (V + 1) / (3 n_faces): for every vertex the faces that use it, ascending (vertex normals are gathered through it); needed when out != NULL
+ *   cam         fp32 (B, 4): sx, sy, tx, ty.  ndc_x = sx (X + tx), ndc_y = sy (Y - ty), ndc_z = -Z for the rotated vertex (X, Y, Z); pixel x = (ndc_x + 1) W / 2,
+ *               pixel y = (1 - ndc_y) H / 2 from the top; samples at pixel centres; smaller ndc_z is nearer; |ndc_z| > 1 is clipped; back faces are culled
+ *   rot         fp32 (B, 3, 3) row-major, applied to the rotated mesh, or NULL
+ *   frames_in   uint8 (B, H, W, 3) or NULL (= black); may be the same buffer as out
+ *   out         uint8 (B, H, W, 3) or NULL: the shaded mesh where it covers a pixel (no blend), the input frame elsewhere
+ *   face_id     int32 (B, H, W) or NULL: visible face, -1 where nothing covers;  depth  fp32 (B, H, W) or NULL: its ndc_z, +infinity where nothing covers
+ *   base_host   HOST pointer to 3 floats, the base colour;  wire_px  with MAED_RENDER_WIREFRAME: a covered pixel is drawn only within this distance of an edge
+ *               of its visible face
+ *   flags       MAED_RENDER_WIREFRAME | MAED_RENDER_RASTER_ONLY (diagnostic: stop after the raster pass, nothing is written to out / face_id / depth) |
+ *               form << MAED_RENDER_FORM_SHIFT: 0 = automatic (2), 1 = every triangle on one lane, 2 = small triangles on a lane, large ones a workgroup each.
+ *               All forms give the same bits.
+ *   workspace   maed_render_mesh_workspace(B, V, n_faces, H, W, flags) bytes, 16-byte aligned
+ * Limits: H, W <= 16384 (8 fractional bits of sub-pixel position, 64-bit edge functions); B H W, B n_faces, B V < 2^31.  Vertices that project to NaN or infinity
+ * remove their triangles; positions beyond 2^22 px are clamped there. */
+#define MAED_RENDER_WIREFRAME 1
+#define MAED_RENDER_RASTER_ONLY 2
+#define MAED_RENDER_FORM_SHIFT 4
+#define MAED_RENDER_FORM_MASK 0xF0
+size_t maed_render_mesh_workspace(int B, int V, int n_faces, int H, int W, int flags);
+int maed_render_mesh(const float* verts, const int32_t* faces, const int32_t* faces_host, const int32_t* vf_off, const int32_t* vf_idx, const float* cam,
+                     const float* rot, const uint8_t* frames_in, uint8_t* out, int32_t* face_id, float* depth, int B, int V, int n_faces, int H, int W,
+                     const float* base_host, float wire_px, int flags, void* workspace, size_t workspace_bytes, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

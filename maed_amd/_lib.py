@@ -164,6 +164,8 @@ SIGNATURES = {
     "maed_adam_step_dev": (i32, [vp, vp, vp, vp, vp, i64, vp, f32, f32, f32, f32, f32, vp]),
     "maed_clip_preprocess_workspace": (C.c_size_t, [i32, i32, i32]),
     "maed_clip_preprocess": (i32, [vp, i64, vp, vp, vp, vp, i32, i32, i32, i32, C.POINTER(f32), i32, i32, vp, vp, C.c_size_t, vp]),
+    "maed_render_mesh_workspace": (C.c_size_t, [i32, i32, i32, i32, i32, i32]),
+    "maed_render_mesh": (i32, [vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, i32, i32, i32, i32, i32, C.POINTER(f32), f32, i32, vp, C.c_size_t, vp]),
 }
 
 _lib = None

@@ -1509,3 +1509,56 @@ def clip_preprocess(blob, offsets, src_bytes, F, N, H, W, mean, std, has_contras
     check(L.lib().maed_clip_preprocess(px, src_bytes, fi, fm, ci, cf, F, N, H, W, norm, int(bool(has_contrast)), form, _p(out), _p(ws), need, _stream()),
           "clip_preprocess")
     return out
+
+
+# ----------------------------------------------------------------------------------------------
+# mesh overlay (csrc/render.hip; the host side lives in maed_amd/render.py)
+# ----------------------------------------------------------------------------------------------
+RENDER_FORM_AUTO, RENDER_FORM_LANE, RENDER_FORM_SPLIT = range(3)
+RENDER_WIREFRAME, RENDER_RASTER_ONLY, RENDER_FORM_SHIFT = 1, 2, 4
+RENDER_MAX_DIM = 16384
+
+
+def render_mesh_workspace(B, V, n_faces, H, W, flags=0):
+    return int(L.lib().maed_render_mesh_workspace(B, V, n_faces, H, W, flags))
+
+
+def render_mesh(verts, faces, faces_host, vf_off, vf_idx, cam, H, W, frames=None, rot=None, out=None, face_id=None, depth=None, base=(1.0, 1.0, 0.9), wireframe=False,
+                wire_px=0.5, form=RENDER_FORM_AUTO, raster_only=False):
+    """maed_render_mesh: verts fp32 (B, V, 3), faces int32 (n_faces, 3) on the device with its host copy `faces_host` (numpy int32; validated by the library on every
+    call) and the vertex -> face CSR (vf_off, vf_idx: render.FaceList builds all four), cam fp32 (B, 4), rot fp32 (B, 3, 3) or None, frames uint8 (B, H, W, 3) or
+    None.  Writes into out (uint8, may be `frames` itself) / face_id (int32 (B, H, W)) / depth (fp32 (B, H, W)), whichever are given; no host synchronisation,
+    current stream."""
+    B, V = int(verts.shape[0]), int(verts.shape[1])
+    n_faces = int(faces.shape[0])
+
+    def want(t, dtype, shape, name, optional=True):
+        if t is None:
+            if optional:
+                return
+            raise L.MaedHipError(f"render_mesh: {name} is required")
+        if t.dtype != dtype or tuple(t.shape) != tuple(shape) or not t.is_contiguous():
+            raise L.MaedHipError(f"render_mesh: {name} must be contiguous {dtype} of shape {tuple(shape)}, got {t.dtype} {tuple(t.shape)}")
+
+    want(verts, torch.float32, (B, V, 3), "verts", False)
+    want(faces, torch.int32, (n_faces, 3), "faces", False)
+    want(cam, torch.float32, (B, 4), "cam", False)
+    want(rot, torch.float32, (B, 3, 3), "rot")
+    want(frames, torch.uint8, (B, H, W, 3), "frames")
+    want(out, torch.uint8, (B, H, W, 3), "out")
+    want(face_id, torch.int32, (B, H, W), "face_id")
+    want(depth, torch.float32, (B, H, W), "depth")
+    want(vf_off, torch.int32, (V + 1,), "vf_off")
+    want(vf_idx, torch.int32, (3 * n_faces,), "vf_idx")
+    fh = None
+    if faces_host is not None:
+        if faces_host.dtype != _np.int32 or faces_host.shape != (n_faces, 3) or not faces_host.flags.c_contiguous:
+            raise L.MaedHipError("render_mesh: faces_host must be a C-contiguous int32 array of the shape of faces")
+        fh = faces_host.ctypes.data
+    flags = (RENDER_WIREFRAME if wireframe else 0) | (RENDER_RASTER_ONLY if raster_only else 0) | (int(form) << RENDER_FORM_SHIFT)
+    need = render_mesh_workspace(B, V, n_faces, H, W, flags)
+    ws = _scratch(need, verts.device, tag="render_mesh") if need else None     # (need == 0: a non-positive size; the library says which)
+    base_c = (C.c_float * 3)(*[float(v) for v in base])
+    check(L.lib().maed_render_mesh(_p(verts), _p(faces), fh, _p(vf_off), _p(vf_idx), _p(cam), _p(rot), _p(frames), _p(out), _p(face_id), _p(depth), B, V, n_faces,
+                                   H, W, base_c, float(wire_px), flags, _p(ws), need, _stream()), "render_mesh")
+    return out

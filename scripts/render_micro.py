@@ -1,0 +1,75 @@
+"""Mesh overlay (csrc/render.hip) in isolation, event-timed: 16 frames of the SMPL-sized procedural mesh (6890 vertices, 13776 faces) at 224 x 224 and at
+1920 x 1080, the mesh a third of the frame height and filling the frame, in both raster forms.  Per row: frames per second of the whole call, the split between
+the raster part (visibility-buffer clear + vertex pass + raster pass, timed with MAED_RENDER_RASTER_ONLY) and the rest (normals + resolve, by difference), and the
+bytes the resolve pass moves (8 B of visibility word + 3 B of frame read + 3 B written per pixel) as a share of HBM peak.  Every window rotates over SETS copies of
+the frames and outputs; with the 8-byte visibility buffer the 1080p working set (265 MB + SETS x 200 MB) is past the 256 MB Infinity Cache, the 224 x 224 one
+(6 MB + SETS x 5 MB) is cache-resident as it would be in use.  The window is repeated REPEATS times; minimum and median are printed.
+The mesh generator is the tests' (tests/_render_ref.py): this script needs the test tree next to it.
+usage: render_micro.py [iters]      (one process; run it under a time limit)"""
+import os
+import sys
+
+import numpy as np
+import torch
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+sys.path.insert(0, os.path.join(ROOT, "tests"))
+import _render_ref as R          # the procedural meshes of the tests
+from maed_amd import ops
+from maed_amd.render import FaceList
+
+iters = int(sys.argv[1]) if len(sys.argv) > 1 else 200
+SETS, REPEATS, B = 4, 3, 16
+HBM_PEAK = 8.0e12
+FORMS = {ops.RENDER_FORM_LANE: "lane", ops.RENDER_FORM_SPLIT: "split"}
+
+
+def timed(call):
+    for i in range(2 * SETS):
+        call(i)
+    torch.cuda.synchronize()
+    us = []
+    for _ in range(REPEATS):
+        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        e0.record()
+        for i in range(iters):
+            call(i)
+        e1.record()
+        torch.cuda.synchronize()
+        us.append(1e3 * e0.elapsed_time(e1) / iters)
+    return min(us), float(np.median(us))
+
+
+def main():
+    assert torch.cuda.is_available(), "render_micro needs a GPU"
+    print(f"device {torch.cuda.get_device_name(0)}; {iters} calls per window over {SETS} buffer sets, {REPEATS} windows per row (min / median)", flush=True)
+    v, f = R.smpl_sized()
+    fl = FaceList(f, len(v))
+    f_t, off, idx = fl.on("cuda")
+    for W, H in ((224, 224), (1920, 1080)):
+        frames = [torch.randint(0, 256, (B, H, W, 3), dtype=torch.uint8, device="cuda") for _ in range(SETS)]
+        outs = [torch.empty_like(x) for x in frames]
+        for label, frac in (("third of the height", 1 / 3), ("filling the frame", 0.98)):
+            cams = torch.from_numpy(np.stack([R.fit_cam(v, H, W, frac, centre=(0.01 * k, 0.0)) for k in range(B)])).cuda()
+            verts = torch.from_numpy(v)[None].repeat(B, 1, 1).contiguous().cuda()
+            ref = None
+            for form in FORMS:
+                full = lambda i: ops.render_mesh(verts, f_t, fl.faces, off, idx, cams, H, W, frames=frames[i % SETS], out=outs[i % SETS], form=form)
+                rast = lambda i: ops.render_mesh(verts, f_t, fl.faces, off, idx, cams, H, W, frames=frames[i % SETS], out=outs[i % SETS], form=form, raster_only=True)
+                t_full, med = timed(full)
+                t_rast, _ = timed(rast)
+                full(0)
+                got = outs[0].clone()
+                same = "" if ref is None else f"  bit-equal to lane: {bool(torch.equal(got, ref))}"
+                ref = got if ref is None else ref
+                resolve = max(t_full - t_rast, 1e-3)
+                nbytes = B * H * W * 14
+                print(f"render {B} x {W}x{H} {label:20s} {FORMS[form]:5s} {t_full:8.1f} / {med:8.1f} us = {B / (t_full * 1e-6):9.0f} frames/s   raster part {t_rast:8.1f} us, "
+                      f"normals + resolve {resolve:8.1f} us moving {nbytes / 1e6:6.1f} MB = {nbytes / (resolve * 1e-6) / 1e12:5.2f} TB/s = "
+                      f"{nbytes / (resolve * 1e-6) / HBM_PEAK:.3f} of HBM peak{same}", flush=True)
+        del frames, outs
+
+
+if __name__ == "__main__":
+    main()
