@@ -46,7 +46,8 @@ def build(force=False, verbose=True):
     os.makedirs(OBJ, exist_ok=True)
     hipcc = _hipcc()
     # every header of csrc/ is a dependency of every object (a header-only edit must never leave stale objects in the library)
-    headers = sorted(os.path.join(CSRC, f) for f in os.listdir(CSRC) if f.endswith((".cuh", ".h"))) + [os.path.join(os.path.dirname(HERE), "include", "maed_hip.h")]
+    # (conv3x3.hip is no source of its own: gemm.hip includes it, so it counts as a header here)
+    headers = sorted(os.path.join(CSRC, f) for f in os.listdir(CSRC) if f.endswith((".cuh", ".h")) or (f.endswith(".hip") and f not in SOURCES)) + [os.path.join(os.path.dirname(HERE), "include", "maed_hip.h")]
     jobs = []
     for src in SOURCES:
         s = os.path.join(CSRC, src)

@@ -191,26 +191,13 @@ __global__ __launch_bounds__(512, 2) void gemm_nt_256_bf16_kernel(const bf16* __
     // ---- epilogue: per (qm, rt) a 32 x 64 piece of the wave's tile through its private LDS staging area
     const bool vec_ok = (e.ldo % 8 == 0) && (e.ldaux % 8 == 0);
     float* stg = reinterpret_cast<float*>(lds_raw) + wave * 32 * GL_ST;
-    const int rr = lane >> 3, cc = (lane & 7) * 8;
-#define G2_STORE_PIECE(accA_, accB_, qm_, rt_)                                                                              \
-    __syncthreads();                                                                                                        \
-    _Pragma("unroll") for (int g = 0; g < 4; ++g) {                                                                         \
-        *reinterpret_cast<float4*>(stg + l31 * GL_ST + 8 * g + 4 * hi) = make_float4(accA_[4 * g], accA_[4 * g + 1], accA_[4 * g + 2], accA_[4 * g + 3]);      \
-        *reinterpret_cast<float4*>(stg + l31 * GL_ST + 32 + 8 * g + 4 * hi) = make_float4(accB_[4 * g], accB_[4 * g + 1], accB_[4 * g + 2], accB_[4 * g + 3]); \
-    }                                                                                                                       \
-    __syncthreads();                                                                                                        \
-    _Pragma("unroll") for (int ps = 0; ps < 4; ++ps) {                                                                      \
-        const int lr = ps * 8 + rr;                                                                                         \
-        const int64_t row = m0 + wr * 128 + (qm_) * 64 + (rt_) * 32 + lr, c0 = n0 + wc * 64 + cc;                           \
-        float v8[8];                                                                                                        \
-        ld8(stg + lr * GL_ST + cc, v8);                                                                                     \
-        if (row < M && c0 < N && !(ablate & 1)) epilogue_store8<EPI, bf16>(e, row, c0, N, v8, vec_ok);                      \
-    }
-    G2_STORE_PIECE(c000, c001, 0, 0)
-    G2_STORE_PIECE(c010, c011, 0, 1)
-    G2_STORE_PIECE(c100, c101, 1, 0)
-    G2_STORE_PIECE(c110, c111, 1, 1)
-#undef G2_STORE_PIECE
+    const int64_t c0 = n0 + wc * 64 + (lane & 7) * 8;
+    const int64_t r0 = m0 + wr * 128;
+    const bool st = !(ablate & 1);
+    epilogue_shuffled<EPI, bf16>(c000, c001, stg, lane, e, r0, c0, M, N, vec_ok, st);           // (qm, rt) = (0, 0): rows qm * 64 + rt * 32 of the wave's 128
+    epilogue_shuffled<EPI, bf16>(c010, c011, stg, lane, e, r0 + 32, c0, M, N, vec_ok, st);
+    epilogue_shuffled<EPI, bf16>(c100, c101, stg, lane, e, r0 + 64, c0, M, N, vec_ok, st);
+    epilogue_shuffled<EPI, bf16>(c110, c111, stg, lane, e, r0 + 96, c0, M, N, vec_ok, st);
 }
 
 template <int EPI>
@@ -226,14 +213,5 @@ static void launch_256(const void* A, int64_t lda, const void* B, int64_t ldb, i
 // called by maed_gemm_nt's dispatcher (gemm.hip); returns false for epilogues this kernel does not carry (fp32 atomics: split-K)
 bool maed_gemm_nt_256_launch(int epilogue, const void* A, int64_t lda, const void* B, int64_t ldb, int64_t M, int64_t N, int64_t K, const EpiArgs& e,
                              hipStream_t s) {
-    switch (epilogue) {
-        case MAED_EPI_STORE: launch_256<MAED_EPI_STORE>(A, lda, B, ldb, M, N, K, e, s); return true;
-        case MAED_EPI_GELU: launch_256<MAED_EPI_GELU>(A, lda, B, ldb, M, N, K, e, s); return true;
-        case MAED_EPI_RESID_F32: launch_256<MAED_EPI_RESID_F32>(A, lda, B, ldb, M, N, K, e, s); return true;
-        case MAED_EPI_MUL_DGELU: launch_256<MAED_EPI_MUL_DGELU>(A, lda, B, ldb, M, N, K, e, s); return true;
-        case MAED_EPI_STORE_F32: launch_256<MAED_EPI_STORE_F32>(A, lda, B, ldb, M, N, K, e, s); return true;
-        case MAED_EPI_TANH: launch_256<MAED_EPI_TANH>(A, lda, B, ldb, M, N, K, e, s); return true;
-        case MAED_EPI_ADD: launch_256<MAED_EPI_ADD>(A, lda, B, ldb, M, N, K, e, s); return true;
-        default: return false;
-    }
+    return epilogue_switch<EPI_SET_STORES>(epilogue, [&](auto epi) { launch_256<decltype(epi)::value>(A, lda, B, ldb, M, N, K, e, s); });
 }

@@ -1,6 +1,8 @@
-// Fused GEMM epilogues shared by the NT GEMM kernels (gemm.hip: 128x128 tiles, gemm256.hip: 256x256 pipelined tiles) and the
-// implicit-GEMM convolution: bias, bias+GELU (+pre-activation), bias+residual (fp32), *GELU', tanh, +aux, fp32 atomics.
+// Fused GEMM epilogues shared by the NT GEMM kernels (gemm.hip: 128x128 tiles, gemm256.hip: 256x256 pipelined tiles, gemm_x3*.hip: split fp32) and the
+// implicit-GEMM convolutions (conv3x3.hip): bias, bias+GELU (+pre-activation), bias+residual (fp32), *GELU', tanh, +aux, fp32 atomics; the LDS shuffle
+// that feeds them full row segments; the runtime -> compile-time epilogue switch of the launchers.
 #pragma once
+#include <type_traits>
 #include "common.cuh"
 
 struct EpiArgs {
@@ -230,6 +232,10 @@ __device__ __forceinline__ void gn_commit(GnRegs& a, const GnTile& g, int lane, 
         }
     }
 }
+static inline bool gn_stats_shape_ok(int64_t channels, int64_t hw) {   // 32 groups of 2^k channels; a 128-row tile spans at most two frames
+    const int64_t cpg = channels / 32;
+    return channels % 32 == 0 && cpg >= 2 && (cpg & (cpg - 1)) == 0 && hw >= 128;
+}
 __device__ __forceinline__ void gn_flush(const GnTile& g, double* sums, int64_t m0, int64_t M, int hw, int tile_cols, int tid, int nthr) {
     const int ngl = ((tile_cols - 1) >> g.sh) + 1;                        // groups this tile's columns touch (<= 64)
     const int64_t n_first = m0 / hw;
@@ -242,7 +248,6 @@ __device__ __forceinline__ void gn_flush(const GnTile& g, double* sums, int64_t 
     }
 }
 
-
 __device__ __forceinline__ int xcd_remap(int bid, int nwg) {
     // bijective remap: blocks that the dispatcher places on XCD x (bid % 8 == x) get a contiguous id range
     const int xcd = bid & 7, q = nwg >> 3, r = nwg & 7;
@@ -253,3 +258,56 @@ __device__ __forceinline__ int xcd_remap(int bid, int nwg) {
 #define GL_ST 68   // fp32 row stride of the epilogue staging area: 272 B -> conflict-free ds_write_b128 per 16-lane group
 typedef maed_lds_void_t lds_void_t;
 typedef maed_glb_void_t glb_void_t;
+
+// ---- LDS-shuffled epilogue of the transposed 32x32 MFMA tiles --------------------------------------------------------------------------
+// In the accumulators a lane owns one output row (4 columns per register group), which would mean 8-byte global accesses scattered over
+// 32 rows per instruction.  Each wave parks a 32 x 64 fp32 piece (accA: columns 0..31, accB: 32..63) in its private staging area `stg`
+// (32 rows of GL_ST floats) and re-reads it so that 8 lanes cover one row's 64 columns: 16/32-byte accesses, full lines per row, for the
+// stores AND for the auxiliary reads of the residual / GELU' epilogues.  The piece's rows are row0 .. row0 + 31 (stored where row < row_end),
+// c0 is the first of this lane's 8 columns.  Every wave of the workgroup calls this (two workgroup barriers: the staging areas overlay the operand
+// tiles); a wave with `active` = false (wave-uniform) only meets the barriers.  do_store = false: the ablation build's "no stores".
+// GN: + GroupNorm statistics of the stored values into gnr (the caller zeroes / commits it).  row_map: row of the piece -> row of `out`.
+struct EpiRowIdentity { __device__ __forceinline__ int64_t operator()(int64_t row) const { return row; } };
+template <int EPI, typename T, bool GN = false, typename RowMap = EpiRowIdentity>
+__device__ __forceinline__ void epilogue_shuffled(const f32x16_t& accA, const f32x16_t& accB, float* stg, int lane, const EpiArgs& e, int64_t row0, int64_t c0,
+                                                  int64_t row_end, int64_t N, bool vec_ok, bool do_store = true, bool active = true, GnRegs* gnr = nullptr,
+                                                  const GnTile* gnt = nullptr, RowMap row_map = RowMap()) {
+    const int l31 = lane & 31, hi = lane >> 5, rr = lane >> 3, cc = (lane & 7) * 8;
+    __syncthreads();                                            // nobody reads the operand tiles / the previous piece any more
+    if (active) {
+#pragma unroll
+        for (int g = 0; g < 4; ++g) {
+            *reinterpret_cast<float4*>(stg + l31 * GL_ST + 8 * g + 4 * hi) = make_float4(accA[4 * g], accA[4 * g + 1], accA[4 * g + 2], accA[4 * g + 3]);
+            *reinterpret_cast<float4*>(stg + l31 * GL_ST + 32 + 8 * g + 4 * hi) = make_float4(accB[4 * g], accB[4 * g + 1], accB[4 * g + 2], accB[4 * g + 3]);
+        }
+    }
+    __syncthreads();
+    if (active) {
+#pragma unroll
+        for (int ps = 0; ps < 4; ++ps) {
+            const int lr = ps * 8 + rr;
+            const int64_t row = row0 + lr;
+            float v8[8];
+            ld8(stg + lr * GL_ST + cc, v8);
+            if (row < row_end && c0 < N && do_store) epilogue_store8<EPI, T>(e, row_map(row), c0, N, v8, vec_ok);
+            if constexpr (GN) { if (row < row_end && c0 < N) gn_acc8<T>(*gnr, *gnt, v8, row); }
+        }
+    }
+}
+
+// ---- runtime epilogue -> compile-time constant ----------------------------------------------------------------------------------------
+// Calls f(std::integral_constant<int, EPI>) for epilogue == EPI if EPI is in SET (a mask of EPI_BIT()s: a launcher instantiates exactly the
+// epilogues its kernel carries); false: not in the set, nothing was called.
+#define EPI_BIT(epi_) (1u << (epi_))
+constexpr unsigned EPI_SET_STORES = EPI_BIT(MAED_EPI_STORE) | EPI_BIT(MAED_EPI_GELU) | EPI_BIT(MAED_EPI_RESID_F32) | EPI_BIT(MAED_EPI_MUL_DGELU) |
+                                    EPI_BIT(MAED_EPI_STORE_F32) | EPI_BIT(MAED_EPI_TANH) | EPI_BIT(MAED_EPI_ADD);      // everything but the fp32 atomics
+constexpr unsigned EPI_SET_ALL = EPI_SET_STORES | EPI_BIT(MAED_EPI_ATOMIC_F32);
+template <unsigned SET, int EPI = 0, typename F>
+static inline bool epilogue_switch(int epilogue, F&& f) {
+    static_assert((SET >> (MAED_EPI_ADD + 1)) == 0, "epilogue_switch walks MAED_EPI_STORE .. MAED_EPI_ADD: raise the bound below together with a new epilogue");
+    if constexpr (EPI > MAED_EPI_ADD) return false;
+    else {
+        if constexpr ((SET >> EPI) & 1u) { if (epilogue == EPI) { f(std::integral_constant<int, EPI>{}); return true; } }
+        return epilogue_switch<SET, EPI + 1>(epilogue, f);
+    }
+}

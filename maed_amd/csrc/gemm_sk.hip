@@ -560,14 +560,5 @@ bool maed_gemm_nt_sk_launch(int epilogue, const void* A, int64_t lda, const void
     }
     if (cut) P.dp_tiles = rounds >= 1 ? (rounds - 1) * G : 0;      // the remainder + one whole round are cut; fewer tiles than workgroups: everything is
     else { P.dp_tiles = (int)T; if (T < G) G = (int)T; }
-    switch (epilogue) {
-        case MAED_EPI_STORE: launch_sk<MAED_EPI_STORE>(A, lda, B, ldb, M, N, K, e, P, G, slabs, flags, s); return true;
-        case MAED_EPI_GELU: launch_sk<MAED_EPI_GELU>(A, lda, B, ldb, M, N, K, e, P, G, slabs, flags, s); return true;
-        case MAED_EPI_RESID_F32: launch_sk<MAED_EPI_RESID_F32>(A, lda, B, ldb, M, N, K, e, P, G, slabs, flags, s); return true;
-        case MAED_EPI_MUL_DGELU: launch_sk<MAED_EPI_MUL_DGELU>(A, lda, B, ldb, M, N, K, e, P, G, slabs, flags, s); return true;
-        case MAED_EPI_STORE_F32: launch_sk<MAED_EPI_STORE_F32>(A, lda, B, ldb, M, N, K, e, P, G, slabs, flags, s); return true;
-        case MAED_EPI_TANH: launch_sk<MAED_EPI_TANH>(A, lda, B, ldb, M, N, K, e, P, G, slabs, flags, s); return true;
-        case MAED_EPI_ADD: launch_sk<MAED_EPI_ADD>(A, lda, B, ldb, M, N, K, e, P, G, slabs, flags, s); return true;
-        default: return false;
-    }
+    return epilogue_switch<EPI_SET_STORES>(epilogue, [&](auto epi) { launch_sk<decltype(epi)::value>(A, lda, B, ldb, M, N, K, e, P, G, slabs, flags, s); });
 }

@@ -1,5 +1,5 @@
 // Internal interface of csrc/gemm_x3.hip (split-bf16 "bf16x3 / bf16x6" GEMMs on fp32 operands) towards the extern "C" entry points of
-// gemm.hip / gemm_tn.hip / attention.  Not part of the C-ABI.
+// gemm.hip / conv3x3.hip / gemm_tn.hip / attention.  Not part of the C-ABI.
 #pragma once
 #include "common.cuh"
 #include "gemm_epilogue.cuh"
@@ -42,7 +42,7 @@ __device__ __forceinline__ f32x16_t mfma_split(const bf16x8_t (&a)[NP], const bf
     return acc;
 }
 
-// 3x3 implicit GEMM geometry: as gemm.hip's Conv3x3Dims.  B element (n, tap, c) = W[b_base + tap * b_tap + n * b_row + c]
+// 3x3 implicit GEMM geometry: as conv3x3.hip's Conv3x3Dims.  B element (n, tap, c) = W[b_base + tap * b_tap + n * b_row + c]
 struct X3ConvDims { int F, H, W, Cin, Ho, Wo, stride, pad_top, pad_left; int64_t b_row, b_tap, b_base; };
 // weight gradient of the stride-1 3x3 convolution: per-pixel 9-bit "tap inside the image" mask (maed_conv3x3_tapmask), Cin, image width
 struct X3TnConv { const uint16_t* tapmask; int Cin, Wimg; };

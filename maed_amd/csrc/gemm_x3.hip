@@ -15,7 +15,7 @@
 // and transposing staging (weight gradients, reduction over rows) come for free: the fragments a MFMA lane needs are picked element by
 // element while packing.  LDS image per operand and plane: 128 rows x 32 k (bf16), rows padded to 80 B (20 dwords = 4 x odd:
 // conflict-free ds_read_b128 fragments and ds_write_b128 rows).  One LDS buffer, the next K tile's global loads in flight under the
-// current tile's MFMAs, LDS-shuffled epilogue as in gemm.hip (all fused epilogues, GroupNorm statistics), XCD-aware tile order.
+// current tile's MFMAs, LDS-shuffled epilogue of gemm_epilogue.cuh (all fused epilogues, GroupNorm statistics), XCD-aware tile order.
 //
 //   gemm_nt_x3_kernel   out = epi(A[M,K] B[N,K]^T)      nn.Linear forward / input gradients, 1x1 convolutions; CONV: 3x3 implicit GEMM
 //   gemm_tn_x3_kernel   dW[N,K] += Y[M,N]^T X[M,K]      weight gradients (reduction over rows), CONV: 3x3 weight gradient over gathered rows
@@ -67,7 +67,7 @@ __device__ __forceinline__ void x3_kstep(const unsigned short* Ap, const unsigne
 // ------------------------------------------------------------------------------------------------------------------------------------
 // NT:  out = epi(A[M,K] B[N,K]^T), fp32 operands, K % 32 == 0, 16-byte aligned rows.
 // CONV: A rows are gathered pixels of a channels_last image (3x3 taps, TF-SAME zero padding, any stride) and B is addressed as
-//       element (n, tap, c) = B[b_base + tap * b_tap + n * b_row + c] -- exactly gemm.hip's conv3x3_glds_bf16_kernel, in fp32.
+//       element (n, tap, c) = B[b_base + tap * b_tap + n * b_row + c] -- exactly conv3x3.hip's conv3x3_glds_bf16_kernel, in fp32.
 // NARROW: 128 x 64 output tile (N <= 64: stage 1 of the R50), the four waves take 32 rows each.
 // ------------------------------------------------------------------------------------------------------------------------------------
 template <int EPI, int NP, bool NARROW, bool CONV, bool GN>
@@ -188,34 +188,19 @@ __global__ __launch_bounds__(256, 2) void gemm_nt_x3_kernel(const float* __restr
         if constexpr (!NARROW) { X3_ATOMIC_EPI(acc10, 1, 0) X3_ATOMIC_EPI(acc11, 1, 1) }
 #undef X3_ATOMIC_EPI
     } else {
-        // LDS-shuffled epilogue (gemm.hip): a lane owns one output row in the accumulators; each wave parks its 32 x 64 half-tile in LDS and re-reads
-        // it with 8 lanes per row -> 32-byte stores / auxiliary reads, full lines per row
+        // LDS-shuffled epilogue (gemm_epilogue.cuh): each wave parks its 32 x 64 half-tile in LDS and re-reads it with 8 lanes per row
+        // -> 32-byte stores / auxiliary reads, full lines per row
         const bool vec_ok = (e.ldo % 8 == 0) && (e.ldaux % 8 == 0);
         float* stg = reinterpret_cast<float*>(lds_raw) + wave * 32 * GL_ST;
-        const int rr = lane >> 3, cc = (lane & 7) * 8;
+        const int64_t col0 = n0 + wc * 64 + (lane & 7) * 8;
         const GnTile gnt = GN ? gn_tile(gn_tab, m0, n0, N, e.gn_hw) : GnTile{nullptr, 0, 0, 0};
         GnRegs gnr;
         if constexpr (GN) gn_zero(gnr);
-#define X3_SHUFFLE_HALF(accA_, accB_, i_)                                                                              \
-        __syncthreads();                                                                                               \
-        _Pragma("unroll") for (int g = 0; g < 4; ++g) {                                                                \
-            *reinterpret_cast<float4*>(stg + l31 * GL_ST + 8 * g + 4 * hi) = make_float4(accA_[4 * g], accA_[4 * g + 1], accA_[4 * g + 2], accA_[4 * g + 3]);      \
-            *reinterpret_cast<float4*>(stg + l31 * GL_ST + 32 + 8 * g + 4 * hi) = make_float4(accB_[4 * g], accB_[4 * g + 1], accB_[4 * g + 2], accB_[4 * g + 3]); \
-        }                                                                                                              \
-        __syncthreads();                                                                                               \
-        _Pragma("unroll") for (int ps = 0; ps < 4; ++ps) {                                                             \
-            const int lr = ps * 8 + rr;                                                                                \
-            const int64_t row = m0 + wr * (NARROW ? 32 : 64) + (i_) * 32 + lr, col0 = n0 + wc * 64 + cc;               \
-            float v8[8];                                                                                               \
-            ld8(stg + lr * GL_ST + cc, v8);                                                                            \
-            if (row < M && col0 < N) epilogue_store8<EPI, float>(e, row, col0, N, v8, vec_ok);                         \
-            if constexpr (GN) { if (row < M && col0 < N) gn_acc8<float>(gnr, gnt, v8, row); }                          \
-        }
-        X3_SHUFFLE_HALF(acc00, acc01, 0)
-        if constexpr (!NARROW) { X3_SHUFFLE_HALF(acc10, acc11, 1) }
-#undef X3_SHUFFLE_HALF
+        const int64_t r0 = m0 + wr * (NARROW ? 32 : 64);
+        epilogue_shuffled<EPI, float, GN>(acc00, acc01, stg, lane, e, r0, col0, M, N, vec_ok, true, true, &gnr, &gnt);
+        if constexpr (!NARROW) epilogue_shuffled<EPI, float, GN>(acc10, acc11, stg, lane, e, r0 + 32, col0, M, N, vec_ok, true, true, &gnr, &gnt);
         if constexpr (GN) {
-            gn_commit(gnr, gnt, lane, n0 + wc * 64 + cc, N);
+            gn_commit(gnr, gnt, lane, col0, N);
             __syncthreads();
             gn_flush(gnt, e.gn_sums, m0, M, e.gn_hw, NARROW ? 64 : 128, tid, 256);
         }
@@ -343,7 +328,7 @@ __global__ __launch_bounds__(256, 2) void gemm_tn_x3_kernel(const float* __restr
 
 }  // namespace
 
-// ---- launchers (C++ linkage; called by the extern "C" entry points of gemm.hip / gemm_tn.hip) -----------------------------------------------
+// ---- launchers (C++ linkage; called by the extern "C" entry points of gemm.hip / conv3x3.hip / gemm_tn.hip) -----------------------------------------------
 
 bool maed_x3_nt_shape_ok(const void* A, int64_t lda, const void* B, int64_t ldb, int64_t K) {
     return K % X3_BK == 0 && lda % 4 == 0 && ldb % 4 == 0 && is_aligned(A, 16) && is_aligned(B, 16);
@@ -378,16 +363,11 @@ int maed_gemm_nt_x3_launch(int epilogue, int np, const void* A, int64_t lda, con
                            int splitk, hipStream_t s) {
     const float* a = (const float*)A; const float* b = (const float*)B;
     MAED_CHECK_ARG(x3_fits32(M, lda, N, ldb), MAED_ERR_SHAPE, "gemm_nt(x3): an operand larger than 4 GB");
-    switch (epilogue) {
-        case MAED_EPI_STORE: launch_nt_np<MAED_EPI_STORE>(np, a, lda, b, ldb, M, N, K, e, 1, s); break;
-        case MAED_EPI_GELU: launch_nt_np<MAED_EPI_GELU>(np, a, lda, b, ldb, M, N, K, e, 1, s); break;
-        case MAED_EPI_RESID_F32: launch_nt_np<MAED_EPI_RESID_F32>(np, a, lda, b, ldb, M, N, K, e, 1, s); break;
-        case MAED_EPI_MUL_DGELU: launch_nt_np<MAED_EPI_MUL_DGELU>(np, a, lda, b, ldb, M, N, K, e, 1, s); break;
-        case MAED_EPI_ATOMIC_F32: launch_nt_np<MAED_EPI_ATOMIC_F32>(np, a, lda, b, ldb, M, N, K, e, splitk, s); break;
-        case MAED_EPI_STORE_F32: launch_nt_np<MAED_EPI_STORE_F32>(np, a, lda, b, ldb, M, N, K, e, 1, s); break;
-        case MAED_EPI_TANH: launch_nt_np<MAED_EPI_TANH>(np, a, lda, b, ldb, M, N, K, e, 1, s); break;
-        case MAED_EPI_ADD: launch_nt_np<MAED_EPI_ADD>(np, a, lda, b, ldb, M, N, K, e, 1, s); break;
-        default: maed_set_error("gemm_nt(x3): bad epilogue %d", epilogue); return MAED_ERR_ARG;
+    // (split-K only under the atomic epilogue)
+    if (!epilogue_switch<EPI_SET_ALL>(epilogue, [&](auto epi) {
+            launch_nt_np<decltype(epi)::value>(np, a, lda, b, ldb, M, N, K, e, decltype(epi)::value == MAED_EPI_ATOMIC_F32 ? splitk : 1, s); })) {
+        maed_set_error("gemm_nt(x3): bad epilogue %d", epilogue);
+        return MAED_ERR_ARG;
     }
     return MAED_OK;
 }

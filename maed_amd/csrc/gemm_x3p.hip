@@ -126,28 +126,13 @@ void gemm_nt_x3p_kernel(const bf16* __restrict__ Ah, const bf16* __restrict__ Al
     }
 #undef XP_ISSUE
 
-    // LDS-shuffled epilogue (gemm.hip / gemm_x3.hip): each wave parks a 32 x 64 piece in LDS and re-reads it with 8 lanes per row
+    // LDS-shuffled epilogue (gemm_epilogue.cuh): each wave parks a 32 x 64 piece in LDS and re-reads it with 8 lanes per row
     const bool vec_ok = (e.ldo % 8 == 0) && (e.ldaux % 8 == 0);
     float* stg = reinterpret_cast<float*>(lds) + wave * 32 * GL_ST;
-    const int rr = lane >> 3, cc = (lane & 7) * 8;
+    const int64_t col0 = n0 + wc * 64 + (lane & 7) * 8;
 #pragma unroll
-    for (int a = 0; a < RM; ++a) {
-        __syncthreads();
-#pragma unroll
-        for (int g = 0; g < 4; ++g) {
-            *reinterpret_cast<float4*>(stg + l31 * GL_ST + 8 * g + 4 * hi) = make_float4(acc[a][0][4 * g], acc[a][0][4 * g + 1], acc[a][0][4 * g + 2], acc[a][0][4 * g + 3]);
-            *reinterpret_cast<float4*>(stg + l31 * GL_ST + 32 + 8 * g + 4 * hi) = make_float4(acc[a][1][4 * g], acc[a][1][4 * g + 1], acc[a][1][4 * g + 2], acc[a][1][4 * g + 3]);
-        }
-        __syncthreads();
-#pragma unroll
-        for (int ps = 0; ps < 4; ++ps) {
-            const int lr = ps * 8 + rr;
-            const int64_t row = m0 + wr * RM * 32 + a * 32 + lr, col0 = n0 + wc * 64 + cc;
-            float v8[8];
-            ld8(stg + lr * GL_ST + cc, v8);
-            if (row < M && col0 < N && !(ablate & 1)) epilogue_store8<EPI, float>(e, row, col0, N, v8, vec_ok);
-        }
-    }
+    for (int a = 0; a < RM; ++a)
+        epilogue_shuffled<EPI, float>(acc[a][0], acc[a][1], stg, lane, e, m0 + wr * RM * 32 + a * 32, col0, M, N, vec_ok, !(ablate & 1));
 }
 
 // fp32 -> (hi, lo) planes, 8 elements per thread and trip; `table` entries are independent tensors (one launch for a block's weights)
@@ -207,11 +192,10 @@ int maed_gemm_nt_x3p_launch(int epilogue, int variant, const void* a_hi, const v
                             int64_t N, int64_t K, const EpiArgs& e, hipStream_t s) {
     const bf16 *Ah = (const bf16*)a_hi, *Al = (const bf16*)a_lo, *Bh = (const bf16*)b_hi, *Bl = (const bf16*)b_lo;
     const int v = variant ? variant : maed_opt(MAED_OPT_X3_PLANES);
-    switch (epilogue) {
-        case MAED_EPI_STORE: launch_x3p_variant<MAED_EPI_STORE>(v, Ah, Al, lda, Bh, Bl, ldb, M, N, K, e, s); break;
-        case MAED_EPI_GELU: launch_x3p_variant<MAED_EPI_GELU>(v, Ah, Al, lda, Bh, Bl, ldb, M, N, K, e, s); break;
-        case MAED_EPI_RESID_F32: launch_x3p_variant<MAED_EPI_RESID_F32>(v, Ah, Al, lda, Bh, Bl, ldb, M, N, K, e, s); break;
-        default: maed_set_error("gemm_nt_planes: epilogue %d is not built for plane operands", epilogue); return MAED_ERR_ARG;
+    constexpr unsigned kPlaneEpilogues = EPI_BIT(MAED_EPI_STORE) | EPI_BIT(MAED_EPI_GELU) | EPI_BIT(MAED_EPI_RESID_F32);
+    if (!epilogue_switch<kPlaneEpilogues>(epilogue, [&](auto epi) { launch_x3p_variant<decltype(epi)::value>(v, Ah, Al, lda, Bh, Bl, ldb, M, N, K, e, s); })) {
+        maed_set_error("gemm_nt_planes: epilogue %d is not built for plane operands", epilogue);
+        return MAED_ERR_ARG;
     }
     return MAED_OK;
 }

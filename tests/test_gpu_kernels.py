@@ -617,6 +617,44 @@ def test_conv3x3_weight_gradient_row_items_64_channels(N, H, W):
     report(f"conv3x3 wgrad rows[{N}x64x{H}x{W}]", (dW - 1.0).permute(0, 3, 1, 2), wd.grad, rtol=2e-3, atol=2e-3 * wd.grad.abs().max().item())
 
 
+@pytest.mark.parametrize("NF,H,W,Cin,Cout", [(2, 14, 14, 64, 128), (1, 16, 16, 128, 136), (2, 11, 13, 64, 64)])
+def test_conv3x3_one_frame_per_workgroup_is_bit_identical_to_the_128_row_tiles(NF, H, W, Cin, Cout):
+    """conv3x3_frame_bf16_kernel (csrc/conv3x3.hip: one frame x 128 channels per workgroup, three-stage copy ring, eight waves of 32 pixel rows, the last ones partly
+    or wholly past the frame) forced with MAED_OPT_CONV3X3_FRAME = 2 against the 128 x 128 tiles (= 0): same K order, same MFMA shape, so the SAME bits -- forward
+    with GroupNorm statistics (where Cout allows), with an `add` operand, and as the input gradient (transposed weight image, flipped taps; Cout % 64 == 0); a ragged
+    last column tile (Cout = 136), and 143 pixels with a 64-column tile.  Cin = 64 is the ring prologue's minimum of 9 K tiles.  The host simulator's test of the
+    same name (tests/test_hostsim_backbone.py), on the device."""
+    ops, L = _ops()
+    lib = L.lib()
+    torch.manual_seed(7)
+    cl = lambda t: t.bfloat16().to(DEV).contiguous(memory_format=torch.channels_last)
+    x, dy, addt = cl(torch.randn(NF, Cin, H, W)), cl(torch.randn(NF, Cout, H, W)), cl(torch.randn(NF, Cout, H, W))
+    wt = (torch.randn(Cout, 3, 3, Cin) * (9 * Cin) ** -0.5).bfloat16().to(DEV)
+    wimg = wt.permute(1, 2, 3, 0).contiguous()             # (3, 3, Cin, Cout): the transposed image maed_weight_std_fwd writes beside the forward weight
+    cpg = Cout // 32
+    gn_ok = Cout % 32 == 0 and cpg >= 2 and (cpg & (cpg - 1)) == 0
+    out = {}
+    old = lib.maed_get_option(L.OPT_CONV3X3_FRAME)
+    try:
+        for mode in (0, 2):
+            assert lib.maed_set_option(L.OPT_CONV3X3_FRAME, mode) == 0
+            sums = torch.zeros(NF, 32, 2, dtype=torch.float64, device=DEV)
+            y = ops.conv3x3(x, wt, 1, gn_sums=sums if gn_ok else None)
+            ya = ops.conv3x3(x, wt, 1, add=addt)
+            dx = ops.conv3x3(dy, wimg, 1, w_layout=1) if Cout % 64 == 0 else y
+            torch.cuda.synchronize()
+            out[mode] = (y, ya, dx, sums)
+    finally:
+        lib.maed_set_option(L.OPT_CONV3X3_FRAME, old)
+    for a, b in zip(out[0][:3], out[2][:3]):
+        assert a.shape == b.shape and torch.equal(a, b)
+    assert torch.allclose(out[0][3], out[2][3], rtol=1e-6, atol=1e-4)       # (fp32 partial sums per lane over other row sets: the statistics agree to fp32 rounding)
+    ref = F.conv2d(x.double(), wt.permute(0, 3, 1, 2).double(), padding=1)
+    assert torch.allclose(out[2][0].double(), ref, rtol=2e-2, atol=2e-2)
+    if Cout % 64 == 0:
+        assert out[2][2].shape == (NF, Cin, H, W)
+
+
 def test_stream_fence_orders_two_streams():
     """maed_stream_fence(from, to): everything enqueued on `from` so far happens before whatever is enqueued on `to` from now on (the fence the host uses for
     side-stream launches instead of framework events).  A long fill on stream A, the fence, a read on stream B: B must see the fill -- 20 rounds, fresh values."""
