@@ -178,7 +178,7 @@ __global__ __launch_bounds__(256, 2) void gemm_nt_mfma_bf16_kernel(const bf16* _
     }
     if (kt < kt_end) GM_COMPUTE_TILE(0);    // odd tile count: the last tile sits in buffer 0
     // D^T tile layout: col (lane & 31) = output row m, row (reg&3) + 8*(reg>>2) + 4*(lane>>5) = output column n
-    const bool vec_ok = (e.ldo % 4 == 0) && (e.ldaux % 4 == 0);
+    const bool vec_ok = epilogue_vec_ok<EPI, bf16, 4>(e);
 #define GM_EPILOGUE(acc_, i_, j_)                                                                     \
     if constexpr (TR) {                                                                               \
         const int64_t row = m0 + wr * 64 + (i_) * 32 + l31;                                           \
@@ -307,7 +307,7 @@ __global__ __launch_bounds__(256, (NBUF == 1 ? 4 : 2)) void gemm_nt_glds_bf16_ke
         GM_EPILOGUE(acc[3], 1, 1);
     } else {
         // LDS-shuffled epilogue (gemm_epilogue.cuh): the wave's two 32 x 64 halves through its staging area (overlays the operand tiles)
-        const bool vec_ok = (e.ldo % 8 == 0) && (e.ldaux % 8 == 0);
+        const bool vec_ok = epilogue_vec_ok<EPI, bf16, 8>(e);
         float* stg = reinterpret_cast<float*>(lds_raw) + wave * 32 * GL_ST;
         const int64_t c0 = n0 + wc * 64 + (lane & 7) * 8;
         const GnTile gnt = GN ? gn_tile(gn_tab, m0, n0, N, e.gn_hw) : GnTile{nullptr, 0, 0, 0};

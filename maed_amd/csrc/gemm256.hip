@@ -189,7 +189,7 @@ __global__ __launch_bounds__(512, 2) void gemm_nt_256_bf16_kernel(const bf16* __
     if (wr == 0) __builtin_amdgcn_s_barrier();        // re-align the two groups: nobody reads operand tiles past this point
 
     // ---- epilogue: per (qm, rt) a 32 x 64 piece of the wave's tile through its private LDS staging area
-    const bool vec_ok = (e.ldo % 8 == 0) && (e.ldaux % 8 == 0);
+    const bool vec_ok = epilogue_vec_ok<EPI, bf16, 8>(e);
     float* stg = reinterpret_cast<float*>(lds_raw) + wave * 32 * GL_ST;
     const int64_t c0 = n0 + wc * 64 + (lane & 7) * 8;
     const int64_t r0 = m0 + wr * 128;

@@ -61,9 +61,23 @@ __device__ __forceinline__ void epilogue_store(const EpiArgs& e, int64_t r, int6
     }
 }
 
-// four consecutive columns c0..c0+3 of one row (c0 % 4 == 0): 8/16-byte accesses when the row base is aligned
+// May a kernel use the W-wide (W = 4, 8) forms below: every row of out / out2 / aux starts a multiple of W elements from a base that is aligned for the
+// widest access of W elements (16 bytes at most: wider ones are split), and so does bias.  out2 counts for GELU only (the ADD mask is read bytewise).
+template <int EPI, typename T, int W>
+__device__ __forceinline__ bool epilogue_vec_ok(const EpiArgs& e) {
+    constexpr bool f32_out = sizeof(T) == 4 || EPI == MAED_EPI_RESID_F32 || EPI == MAED_EPI_STORE_F32 || EPI == MAED_EPI_ATOMIC_F32;
+    constexpr uintptr_t out_mask = (W * (f32_out ? 4 : 2) < 16 ? W * (f32_out ? 4 : 2) : 16) - 1;
+    constexpr uintptr_t aux_mask = (W * (EPI == MAED_EPI_RESID_F32 ? 4 : (int)sizeof(T)) < 16 ? W * (EPI == MAED_EPI_RESID_F32 ? 4 : (int)sizeof(T)) : 16) - 1;
+    uintptr_t misaligned = ((uintptr_t)e.out & out_mask) | ((uintptr_t)e.aux & aux_mask) | ((uintptr_t)e.bias & 15);
+    if constexpr (EPI == MAED_EPI_GELU) misaligned |= (uintptr_t)e.out2 & out_mask;
+    return e.ldo % W == 0 && e.ldaux % W == 0 && misaligned == 0;
+}
+
+// four consecutive columns c0..c0+3 of one row (c0 % 4 == 0): 8/16-byte accesses when the row base is aligned.  bf16 storage only (the register-staged
+// MFMA kernel): the twin / plane outputs of the fp32 products are written by the scalar and the 8-wide forms
 template <int EPI, typename T>
 __device__ __forceinline__ void epilogue_store4(const EpiArgs& e, int64_t r, int64_t c0, int64_t N, const float (&acc)[4], bool vec_ok) {
+    static_assert(sizeof(T) == 2, "epilogue_store4 carries no twin / lo outputs: fp32 storage goes through epilogue_store / epilogue_store8");
     if (!(vec_ok && c0 + 4 <= N)) {
 #pragma unroll
         for (int j = 0; j < 4; ++j) if (c0 + j < N) epilogue_store<EPI, T>(e, r, c0 + j, acc[j]);
@@ -79,14 +93,12 @@ __device__ __forceinline__ void epilogue_store4(const EpiArgs& e, int64_t r, int
         if (e.bias) { float b[4]; ld4(e.bias + c0, b); v[0] += b[0]; v[1] += b[1]; v[2] += b[2]; v[3] += b[3]; }
     }
     if constexpr (EPI == MAED_EPI_STORE) {
-        if (sizeof(T) != 4 || e.out) st4((T*)e.out + r * e.ldo + c0, v);
-        if constexpr (sizeof(T) == 4) { if (e.twin) st4((bf16*)e.twin + r * e.ldo + c0, v); }
+        st4((T*)e.out + r * e.ldo + c0, v);
     } else if constexpr (EPI == MAED_EPI_GELU) {
-        if (e.out2) { if (sizeof(T) == 4 && e.out2_bf16) st4((bf16*)e.out2 + r * e.ldo + c0, v); else st4((T*)e.out2 + r * e.ldo + c0, v); }
+        if (e.out2) st4((T*)e.out2 + r * e.ldo + c0, v);
         // activation of the STORED (rounded) pre-activation, as the backward sees it -- rounded in registers, not read back
         float a[4] = {gelu_fwd<T>(round_to<T>(v[0])), gelu_fwd<T>(round_to<T>(v[1])), gelu_fwd<T>(round_to<T>(v[2])), gelu_fwd<T>(round_to<T>(v[3]))};
-        if (sizeof(T) != 4 || e.out) st4((T*)e.out + r * e.ldo + c0, a);
-        if constexpr (sizeof(T) == 4) { if (e.twin) st4((bf16*)e.twin + r * e.ldo + c0, a); }
+        st4((T*)e.out + r * e.ldo + c0, a);
     } else if constexpr (EPI == MAED_EPI_RESID_F32) {
         float x[4]; ld4((const float*)e.aux + r * e.ldaux + c0, x);
         float o[4] = {x[0] + v[0], x[1] + v[1], x[2] + v[2], x[3] + v[3]};

@@ -724,22 +724,7 @@ def test_frame_barrier_timeout_is_reported_and_the_library_falls_back():
 
 
 # ---- round 6: the persistent K-stream GEMM (csrc/gemm_sk.hip) -----------------------------------------------------------------------------
-class _sk_mode:
-    """MAED_OPT_SK for the duration of a block (2 = whole tiles only, 3 = stream-K cuts whenever the tiles do not fill whole rounds of the grid)"""
-
-    def __init__(self, mode, grid=0):
-        self.mode, self.grid = mode, grid
-
-    def __enter__(self):
-        _, L = _ops()
-        self.lib = L.lib()
-        self.old = (self.lib.maed_get_option(L.OPT_SK), self.lib.maed_get_option(L.OPT_SK_GRID))
-        assert self.lib.maed_set_option(L.OPT_SK, self.mode) == 0 and self.lib.maed_set_option(L.OPT_SK_GRID, self.grid) == 0
-
-    def __exit__(self, *a):
-        _, L = _ops()
-        self.lib.maed_set_option(L.OPT_SK, self.old[0])
-        self.lib.maed_set_option(L.OPT_SK_GRID, self.old[1])
+from _gemm_cases import _sk_mode  # noqa: E402  (shared with tests/test_gpu_gemm_epilogues.py)
 
 
 @pytest.mark.parametrize("M,N,K", [(300, 264, 128), (197 * 8, 512, 256), (1000, 1536, 512), (777, 256, 2048), (25216, 512, 512), (32896, 768, 3072)])
