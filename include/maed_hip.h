@@ -667,6 +667,42 @@ int maed_render_mesh(const float* verts, const int32_t* faces, const int32_t* fa
                      const float* rot, const uint8_t* frames_in, uint8_t* out, int32_t* face_id, float* depth, int B, int V, int n_faces, int H, int W,
                      const float* base_host, float wire_px, int flags, void* workspace, size_t workspace_bytes, void* stream);
 
+/* ---- stage-1 encoder (MAED(encoder='cnn'), lib/models/maed.py:35-37: torchvision-layout ResNet-50): BatchNorm2d, MaxPool2d(3, 2, 1), global average pool ----
+ * Activations are channels_last: row-major (M = N*H*W rows, C) in `dtype` (MAED_F32 / MAED_BF16), C % 8 == 0, M < 2^31, 16-byte aligned; mean / rstd / gamma /
+ * beta / running buffers / sums are fp32 (C), 16-byte aligned.  No atomics: every result is bit-identical from run to run.
+ *
+ * maed_batchnorm_chunks(M): row chunks the reductions stripe M rows over; `partials` is caller scratch of chunks * C * 2 doubles (written, never read before).
+ * maed_batchnorm_stats: partials[chunk][c] = (sum x, sum x^2) of the chunk's rows, then maed_batchnorm_finalize over them with count = M.
+ * maed_batchnorm_finalize: sums (chunks, C, 2) fp64 are added in a fixed order; mean = S / count, var = Q / count - mean^2 (biased), rstd = 1 / sqrt(var + eps);
+ *   running_mean / running_var (each may be NULL) <- (1 - momentum) * old + momentum * (mean / var * count / (count - 1)).  Taking (sums, count) it also serves
+ *   partials that were reduced across ranks first.  mean_lo (optional, fp32 (C)): the part of the fp64 mean that fp32 `mean` rounds away; the backward entry
+ *   points subtract both (mean_lo == NULL there: zero), so that xhat = (x - mean) rstd stays accurate for a channel that is almost constant over the batch.
+ * maed_batchnorm_apply_fwd: y = act(gamma * (x - mean) * rstd + beta [+ residual]), act = ReLU when relu != 0.  relu_mask (optional; residual and relu only):
+ *   M * C / 8 bytes, the layout of maed_groupnorm_fwd's relu_mask (bit j of byte (row, c / 8) = output channel 8 * (c / 8) + j > 0).  Eval mode is this entry
+ *   point with mean = running_mean, rstd = 1 / sqrt(running_var + eps).
+ * maed_batchnorm_bwd_reduce: dy' = dy masked by the ReLU (relu_mask when given, else recomputed from x as the forward did: no residual was added);
+ *   sums[c] (optional, fp32 (C, 2)) = (sum dy', sum dy' xhat), dbeta[c] += sum dy', dgamma[c] += sum dy' xhat (each optional).
+ * maed_batchnorm_bwd_apply: dx = gamma * rstd * (dy' - sums[c][0] / M - xhat * sums[c][1] / M); sums == NULL (frozen statistics): dx = dy' * gamma * rstd;
+ *   dres (optional) = dy'. */
+int maed_batchnorm_chunks(int64_t M);
+int maed_batchnorm_stats(const void* x, int64_t M, int C, int dtype, double* partials, float eps, float* mean, float* mean_lo, float* rstd, float* running_mean,
+                         float* running_var, float momentum, void* stream);
+int maed_batchnorm_finalize(const double* sums, int chunks, int C, double count, float eps, float* mean, float* mean_lo, float* rstd, float* running_mean,
+                            float* running_var, float momentum, void* stream);
+int maed_batchnorm_apply_fwd(const void* x, const void* residual, const float* mean, const float* rstd, const float* gamma, const float* beta, void* y,
+                             uint8_t* relu_mask, int64_t M, int C, int relu, int dtype, void* stream);
+int maed_batchnorm_bwd_reduce(const void* x, const void* dy, const uint8_t* relu_mask, const float* mean, const float* mean_lo, const float* rstd, const float* gamma,
+                              const float* beta, double* partials, float* sums, float* dgamma, float* dbeta, int64_t M, int C, int relu, int dtype, void* stream);
+int maed_batchnorm_bwd_apply(const void* x, const void* dy, const uint8_t* relu_mask, const float* mean, const float* mean_lo, const float* rstd, const float* gamma,
+                             const float* beta, const float* sums, void* dx, void* dres, int64_t M, int C, int relu, int dtype, void* stream);
+/* MaxPool2d(kernel 3, stride 2, padding 1 with -inf) on channels_last x (N,H,W,C), C % 8 == 0: y (N, (H-1)/2+1, (W-1)/2+1, C) and the winning tap per output
+ * element (idx, uint8, same shape as y; ATen tie / NaN rule, as maed_maxpool3s2_same_*); backward gathers dx. */
+int maed_maxpool3s2p1_fwd(const void* x, void* y, uint8_t* idx, int N, int H, int W, int C, int dtype, void* stream);
+int maed_maxpool3s2p1_bwd(const void* dy, const uint8_t* idx, void* dx, int N, int H, int W, int C, int dtype, void* stream);
+/* AdaptiveAvgPool2d(1): x (F, HW, C) in `dtype` -> y fp32 (F, C); backward dx[f][hw][c] = dy[f][c] / HW in `dtype`. */
+int maed_avgpool_fwd(const void* x, float* y, int F, int HW, int C, int dtype, void* stream);
+int maed_avgpool_bwd(const float* dy, void* dx, int F, int HW, int C, int dtype, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -166,6 +166,16 @@ SIGNATURES = {
     "maed_clip_preprocess": (i32, [vp, i64, vp, vp, vp, vp, i32, i32, i32, i32, C.POINTER(f32), i32, i32, vp, vp, C.c_size_t, vp]),
     "maed_render_mesh_workspace": (C.c_size_t, [i32, i32, i32, i32, i32, i32]),
     "maed_render_mesh": (i32, [vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, i32, i32, i32, i32, i32, C.POINTER(f32), f32, i32, vp, C.c_size_t, vp]),
+    "maed_batchnorm_chunks": (i32, [i64]),
+    "maed_batchnorm_stats": (i32, [vp, i64, i32, i32, vp, f32, vp, vp, vp, vp, vp, f32, vp]),
+    "maed_batchnorm_finalize": (i32, [vp, i32, i32, C.c_double, f32, vp, vp, vp, vp, vp, f32, vp]),
+    "maed_batchnorm_apply_fwd": (i32, [vp, vp, vp, vp, vp, vp, vp, vp, i64, i32, i32, i32, vp]),
+    "maed_batchnorm_bwd_reduce": (i32, [vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, i64, i32, i32, i32, vp]),
+    "maed_batchnorm_bwd_apply": (i32, [vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, i64, i32, i32, i32, vp]),
+    "maed_maxpool3s2p1_fwd": (i32, [vp, vp, vp, i32, i32, i32, i32, i32, vp]),
+    "maed_maxpool3s2p1_bwd": (i32, [vp, vp, vp, i32, i32, i32, i32, i32, vp]),
+    "maed_avgpool_fwd": (i32, [vp, vp, i32, i32, i32, i32, vp]),
+    "maed_avgpool_bwd": (i32, [vp, vp, i32, i32, i32, i32, vp]),
 }
 
 _lib = None

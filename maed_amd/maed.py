@@ -7,7 +7,7 @@
 Extra keyword arguments (defaults = the reference's hard-coded values): embed_dim=768, max_seqlen=16,
 img_size=224, compute_dtype=torch.bfloat16 (torch.float32 = parity mode), impl, smpl_arrays
 (dict with the SMPL model arrays; None -> deterministic synthetic stand-in, see maed_amd/smpl.py).
-encoder='ste' only ('cnn' is the stage-1 torchvision ResNet-50); decoder 'ktd' (configured, config_stage2.yaml:70-78)
+encoder 'ste', or 'cnn' (stage 1, config_stage1.yaml: the torchvision-layout BatchNorm ResNet-50 of maed_amd/resnet.py, 2048 features per frame); decoder 'ktd' (configured, config_stage2.yaml:70-78)
 or 'iterative' (spin.py Regressor; extra kwarg smpl_mean_params).
 """
 import torch
@@ -24,12 +24,16 @@ class MAED(nn.Module):
                  smpl_arrays=None, backbone_f32_matmul=None, **kwargs):
         super().__init__()
         self.encoder_type = encoder
-        if encoder.lower() != 'ste':
-            raise NotImplementedError(encoder)       # maed.py:41 ('cnn' = stage-1 torchvision ResNet-50: out of scope)
-        self.encoder = vit_custom_resnet50_224_in21k(num_blocks, num_heads, st_mode, embed_dim=embed_dim, img_size=img_size,
-                                                     max_seqlen=max_seqlen, compute_dtype=compute_dtype, impl=impl)
-        # compute_dtype = float32: the backbone's own fp32 matmul engine (resnetv2.ResNetV2.f32_matmul); None = the process-wide mode
-        self.encoder.patch_embed.backbone.f32_matmul = backbone_f32_matmul
+        if encoder.lower() == 'cnn':                 # maed.py:35-37: torchvision resnet50, fc = Identity
+            from .resnet import resnet50
+            self.encoder = resnet50(compute_dtype=compute_dtype, f32_matmul=backbone_f32_matmul)
+        elif encoder.lower() == 'ste':
+            self.encoder = vit_custom_resnet50_224_in21k(num_blocks, num_heads, st_mode, embed_dim=embed_dim, img_size=img_size,
+                                                         max_seqlen=max_seqlen, compute_dtype=compute_dtype, impl=impl)
+            # compute_dtype = float32: the backbone's own fp32 matmul engine (resnetv2.ResNetV2.f32_matmul); None = the process-wide mode
+            self.encoder.patch_embed.backbone.f32_matmul = backbone_f32_matmul
+        else:
+            raise NotImplementedError(encoder)       # maed.py:41
         self.decoder_type = decoder
         if decoder.lower() == 'ktd':                 # maed.py:24-29
             self.decoder = KTD(feat_dim=self.encoder.num_features, hidden_dim=hidden_dim, smpl_arrays=smpl_arrays)
@@ -51,7 +55,7 @@ class MAED(nn.Module):
     def forward(self, x, J_regressor=None, **kwargs):
         batch_size, seqlen = x.shape[:2]
         x = x.reshape(-1, x.shape[-3], x.shape[-2], x.shape[-1])
-        xf = self.encoder(x, seqlen=seqlen)
+        xf = self.encoder(x) if self.encoder_type.lower() == 'cnn' else self.encoder(x, seqlen=seqlen)      # maed.py:57
         output = self.decoder(xf, seqlen=seqlen, J_regressor=J_regressor, **kwargs)
         output['theta'] = output['theta'].reshape(batch_size, seqlen, -1)
         output['verts'] = output['verts'].reshape(batch_size, seqlen, -1, 3)

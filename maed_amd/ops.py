@@ -1562,3 +1562,252 @@ def render_mesh(verts, faces, faces_host, vf_off, vf_idx, cam, H, W, frames=None
     check(L.lib().maed_render_mesh(_p(verts), _p(faces), fh, _p(vf_off), _p(vf_idx), _p(cam), _p(rot), _p(frames), _p(out), _p(face_id), _p(depth), B, V, n_faces,
                                    H, W, base_c, float(wire_px), flags, _p(ws), need, _stream()), "render_mesh")
     return out
+
+
+# ----------------------------------------------------------------------------------------------
+# stage-1 encoder (maed_amd/resnet.py): BatchNorm2d, MaxPool2d(3, 2, 1), global average pool (csrc/batchnorm.hip), unstandardised weight images
+# ----------------------------------------------------------------------------------------------
+def batchnorm_scratch(M, C_, device):
+    """caller scratch of the BatchNorm reductions: (chunks, C, 2) fp64 partial sums, written with plain stores (no zero-fill needed)"""
+    return torch.empty(int(L.lib().maed_batchnorm_chunks(M)) * C_ * 2, dtype=torch.float64, device=device)
+
+
+def batchnorm_stats(x2, eps, running_mean=None, running_var=None, momentum=0.1, partials=None):
+    """per-channel (mean, rstd) of x2 (M, C) over its rows -- biased variance, eps inside the root -- and, when given, the in-place update of the running buffers
+    (unbiased variance).  Returns (mean, rstd, mean_lo): mean_lo is what fp32 `mean` rounds away of the fp64 mean (the backward subtracts both).
+    Deterministic: per-workgroup partials + a fixed-order combine, no atomics."""
+    M, C_ = x2.shape
+    partials = batchnorm_scratch(M, C_, x2.device) if partials is None else partials
+    stat = torch.empty(3, C_, dtype=torch.float32, device=x2.device)
+    mean, mean_lo, rstd = stat[0], stat[1], stat[2]
+    check(L.lib().maed_batchnorm_stats(_p(x2), M, C_, dt_code(x2.dtype), _p(partials), eps, _p(mean), _p(mean_lo), _p(rstd), _p(running_mean), _p(running_var), momentum,
+                                       _stream()), "batchnorm_stats")
+    return mean, rstd, mean_lo
+
+
+def batchnorm_apply(x2, mean, rstd, gamma, beta, residual=None, relu=False, want_mask=False):
+    """y = act(gamma (x - mean) rstd + beta [+ residual]) on (M, C) rows; want_mask (residual and relu only): + the 1-bit-per-element ReLU mask"""
+    M, C_ = x2.shape
+    y = torch.empty_like(x2)
+    mask = torch.empty(M * (C_ // 8), dtype=torch.uint8, device=x2.device) if (want_mask and relu and residual is not None) else None
+    check(L.lib().maed_batchnorm_apply_fwd(_p(x2), _p(residual), _p(mean), _p(rstd), _p(gamma), _p(beta), _p(y), _p(mask), M, C_, int(relu), dt_code(x2.dtype), _stream()),
+          "batchnorm_apply_fwd")
+    return y, mask
+
+
+def batchnorm_bwd(x2, dy2, mean, rstd, gamma, beta, mask=None, relu=False, frozen=False, dgamma=None, dbeta=None, want_dres=False, partials=None, mean_lo=None):
+    """(dx, dres) of batchnorm_apply; dgamma / dbeta (fp32 (C), optional) are ACCUMULATED into.  frozen: the statistics were constants (eval mode): dx = dy' gamma rstd."""
+    M, C_ = x2.shape
+    dx = torch.empty_like(x2)
+    dres = torch.empty_like(x2) if want_dres else None
+    sums = None
+    if not frozen or dgamma is not None or dbeta is not None:
+        partials = batchnorm_scratch(M, C_, x2.device) if partials is None else partials
+        sums = None if frozen else torch.empty(C_ * 2, dtype=torch.float32, device=x2.device)
+        check(L.lib().maed_batchnorm_bwd_reduce(_p(x2), _p(dy2), _p(mask), _p(mean), _p(mean_lo), _p(rstd), _p(gamma), _p(beta), _p(partials), _p(sums), _p(dgamma), _p(dbeta), M, C_,
+                                                int(relu), dt_code(x2.dtype), _stream()), "batchnorm_bwd_reduce")
+    check(L.lib().maed_batchnorm_bwd_apply(_p(x2), _p(dy2), _p(mask), _p(mean), _p(mean_lo), _p(rstd), _p(gamma), _p(beta), _p(sums), _p(dx), _p(dres), M, C_, int(relu),
+                                           dt_code(x2.dtype), _stream()), "batchnorm_bwd_apply")
+    return dx, dres
+
+
+def _rows(t):
+    """(N, C, H, W) channels_last -> its (N*H*W, C) row matrix (a view)"""
+    N, C_, H, W = t.shape
+    return t.permute(0, 2, 3, 1).reshape(N * H * W, C_)
+
+
+class BatchNormFn(torch.autograd.Function):
+    """y = act(BatchNorm2d(x) [+ residual]) on channels_last tensors (maed_batchnorm_*).  training: batch statistics, `buffers` = (running_mean, running_var) or None
+    are updated in place; otherwise the statistics are the running buffers (frozen in the backward).  Saved for the backward: x, mean / rstd (C floats each) and --
+    only when a residual was added before the ReLU -- one bit per element; without a residual the ReLU decision is recomputed from x."""
+
+    @staticmethod
+    def forward(ctx, x, residual, gamma, beta, buffers, training, momentum, eps, relu):
+        N, C_, H, W = x.shape
+        x = x.contiguous(memory_format=torch.channels_last)
+        if residual is not None:
+            residual = residual.contiguous(memory_format=torch.channels_last).to(x.dtype)
+        x2 = _rows(x)
+        if training:
+            rm, rv = buffers if buffers is not None else (None, None)
+            mean, rstd, mean_lo = batchnorm_stats(x2, eps, rm, rv, momentum)
+        else:
+            rm, rv = buffers
+            mean, rstd, mean_lo = rm.float().clone(), torch.rsqrt(rv.float() + eps), None
+        need_mask = relu and residual is not None and any(ctx.needs_input_grad[:4])
+        y2, mask = batchnorm_apply(x2, mean, rstd, gamma, beta, None if residual is None else _rows(residual), relu, want_mask=need_mask)
+        ctx.save_for_backward(x, mask, mean, rstd, gamma, beta, mean_lo)
+        ctx.relu, ctx.has_res, ctx.frozen = relu, residual is not None, not training
+        return y2.view(N, H, W, C_).permute(0, 3, 1, 2)
+
+    @staticmethod
+    def backward(ctx, dy):
+        x, mask, mean, rstd, gamma, beta, mean_lo = ctx.saved_tensors
+        N, C_, H, W = x.shape
+        dy = dy.contiguous(memory_format=torch.channels_last).to(x.dtype)
+        want_affine = ctx.needs_input_grad[2] or ctx.needs_input_grad[3]
+        dgamma = torch.zeros(C_, dtype=torch.float32, device=x.device) if want_affine else None
+        dbeta = torch.zeros(C_, dtype=torch.float32, device=x.device) if want_affine else None
+        dx2, dres2 = batchnorm_bwd(_rows(x), _rows(dy), mean, rstd, gamma, beta, mask, ctx.relu, ctx.frozen, dgamma, dbeta, want_dres=ctx.has_res, mean_lo=mean_lo)
+        dx = dx2.view(N, H, W, C_).permute(0, 3, 1, 2)
+        dres = dres2.view(N, H, W, C_).permute(0, 3, 1, 2) if dres2 is not None else None
+        return dx, dres, dgamma, dbeta, None, None, None, None, None
+
+
+class MaxPool3s2P1Fn(torch.autograd.Function):
+    """MaxPool2d(3, 2, padding=1) on a channels_last tensor (maed_maxpool3s2p1_fwd/bwd): no -inf padded copy, gather backward"""
+
+    @staticmethod
+    def forward(ctx, x):
+        N, C_, H, W = x.shape
+        x = x.contiguous(memory_format=torch.channels_last)
+        Ho, Wo = (H - 1) // 2 + 1, (W - 1) // 2 + 1
+        y = torch.empty((N, C_, Ho, Wo), dtype=x.dtype, device=x.device, memory_format=torch.channels_last)
+        idx = torch.empty(N * Ho * Wo * C_, dtype=torch.uint8, device=x.device)
+        check(L.lib().maed_maxpool3s2p1_fwd(_p(x), _p(y), _p(idx), N, H, W, C_, dt_code(x.dtype), _stream()), "maxpool3s2p1_fwd")
+        ctx.save_for_backward(idx)
+        ctx.geom = (N, C_, H, W)
+        return y
+
+    @staticmethod
+    def backward(ctx, dy):
+        idx, = ctx.saved_tensors
+        N, C_, H, W = ctx.geom
+        dy = dy.contiguous(memory_format=torch.channels_last)
+        dx = torch.empty((N, C_, H, W), dtype=dy.dtype, device=dy.device, memory_format=torch.channels_last)
+        check(L.lib().maed_maxpool3s2p1_bwd(_p(dy), _p(idx), _p(dx), N, H, W, C_, dt_code(dy.dtype), _stream()), "maxpool3s2p1_bwd")
+        return dx
+
+
+class GlobalAvgPoolFn(torch.autograd.Function):
+    """AdaptiveAvgPool2d(1) + flatten on a channels_last tensor: (F, C, H, W) -> (F, C) fp32 (maed_avgpool_fwd/bwd)"""
+
+    @staticmethod
+    def forward(ctx, x):
+        F_, C_, H, W = x.shape
+        x = x.contiguous(memory_format=torch.channels_last)
+        y = torch.empty(F_, C_, dtype=torch.float32, device=x.device)
+        check(L.lib().maed_avgpool_fwd(_p(x), _p(y), F_, H * W, C_, dt_code(x.dtype), _stream()), "avgpool_fwd")
+        ctx.geom, ctx.dtype = (F_, C_, H, W), x.dtype
+        return y
+
+    @staticmethod
+    def backward(ctx, dy):
+        F_, C_, H, W = ctx.geom
+        dy = _c(dy.float())
+        dx = torch.empty((F_, C_, H, W), dtype=ctx.dtype, device=dy.device, memory_format=torch.channels_last)
+        check(L.lib().maed_avgpool_bwd(_p(dy), _p(dx), F_, H * W, C_, dt_code(ctx.dtype), _stream()), "avgpool_bwd")
+        return dx
+
+
+class WeightImageFn(torch.autograd.Function):
+    """WeightStdFn without the standardisation: the compute-dtype images of plain convolution weights, once per pass for all convolutions of `owner`.
+    Outputs: per convolution the logical (O, I, kh, kw) view over (O, kh, kw, I) storage.  For the convolutions listed in owner._direct_convs (they run on the
+    library's kernels: Conv1x1Fn / Conv3x3Fn / Conv3x3S2P1Fn / StemConvFn) owner._w_t[i] is the transposed image (kh*kw*I, O) and owner._dw_slices[i] the zeroed
+    fp32 (O, kh*kw*I) slice their weight gradient accumulates into; the backward permutes those slices (plus whatever autograd carried for the convolutions that
+    ran on the framework) back to (O, I, kh, kw) and returns them as the weights' gradients.
+    The images are rebuilt when the weights changed (ops.WEIGHT_EPOCH, tensor versions), not per call."""
+
+    @staticmethod
+    def forward(ctx, owner, dtype, *weights):
+        direct = sorted(getattr(owner, "_direct_convs", ()) or ())
+        key = (WEIGHT_EPOCH, dtype, tuple(direct), tuple((w.data_ptr(), w._version, tuple(w.shape)) for w in weights))
+        cache = getattr(owner, "_image_cache", None)
+        if cache is None or cache[0] != key:
+            imgs = [w.detach().permute(0, 2, 3, 1).to(dtype).contiguous() for w in weights]                      # (O, kh, kw, I)
+            w_t = {i: imgs[i].view(imgs[i].shape[0], -1).t().contiguous() for i in direct}                       # (kh*kw*I, O)
+            cache = owner._image_cache = (key, imgs, w_t)
+            WeightImageFn.rebuilds += 1
+        _, imgs, owner._w_t = cache
+        ctx.shapes = [tuple(w.shape) for w in weights]
+        ctx.device = weights[0].device
+        ctx.set_materialize_grads(False)
+        owner._dw_slices = {}
+        if direct and ReportingFn._grad_mode_at_apply and any(ctx.needs_input_grad):
+            arena = torch.zeros(sum(weights[i].numel() for i in direct), dtype=torch.float32, device=weights[0].device)
+            o = 0
+            for i in direct:
+                owner._dw_slices[i] = arena[o:o + weights[i].numel()].view(weights[i].shape[0], -1)
+                o += weights[i].numel()
+        ctx.dw_slices = owner._dw_slices
+        return tuple(im.permute(0, 3, 1, 2) for im in imgs)
+
+    rebuilds = 0     # image rebuilds so far (tests: once per weight epoch)
+
+    @classmethod
+    def apply(cls, *args):
+        ReportingFn._grad_mode_at_apply = torch.is_grad_enabled()
+        return super().apply(*args)
+
+    @staticmethod
+    def backward(ctx, *gouts):
+        side_stream_join(ctx.device)       # the fp32 dW slices are written on the side stream
+        grads = []
+        for i, (shape, g) in enumerate(zip(ctx.shapes, gouts)):
+            O, I, kh, kw = shape
+            d = ctx.dw_slices.get(i)
+            gw = d.view(O, kh, kw, I).permute(0, 3, 1, 2) if d is not None else None
+            if g is not None:
+                gw = g.float() if gw is None else gw + g.float()
+            grads.append(gw)
+        return (None, None) + tuple(grads)
+
+
+class Conv3x3S2P1Fn(torch.autograd.Function):
+    """3x3 convolution, stride 2, zero padding 1 (conv2 of the first block of layer2..4 of the torchvision ResNet-50) on the library's implicit-GEMM kernels, which take
+    the padding explicitly: Conv3x3Fn derives TF-SAME padding from the input size, which at an even input size is (0, 1), not (1, 0).  Forward maed_conv3x3_fwd,
+    input gradient maed_conv3x3_s2_dgrad, weight gradient maed_conv3x3_s2_wgrad; whatever a kernel's precondition excludes takes the framework's backward.
+    w / wt / dw as Conv3x3Fn's."""
+
+    @staticmethod
+    def forward(ctx, x, w, wt=None, dw=None, prec=None):
+        x = x.contiguous(memory_format=torch.channels_last)
+        N, I, H, W = x.shape
+        O = w.shape[0]
+        Ho, Wo = (H - 1) // 2 + 1, (W - 1) // 2 + 1
+        w_taps = w.permute(0, 2, 3, 1)
+        w_taps = w_taps if w_taps.is_contiguous() else w_taps.contiguous()
+        y = torch.empty(N, O, Ho, Wo, dtype=x.dtype, device=x.device, memory_format=torch.channels_last)
+        check(L.lib().maed_conv3x3_fwd(_p(x), _p(w_taps), _p(_zero_page(x.device)), _p(y), N, H, W, I, O, 2, 1, 1, Ho, Wo, None, 0, mm_code(x.dtype, prec), None, _stream()),
+              "conv3x3_fwd")
+        ctx.save_for_backward(x, w)
+        ctx.wt, ctx.dw = wt, dw
+        return y
+
+    @staticmethod
+    def backward(ctx, dy):
+        x, w = ctx.saved_tensors
+        wt, dw_slice = ctx.wt, ctx.dw
+        dy = dy.contiguous(memory_format=torch.channels_last)
+        N, I, H, W = x.shape
+        O, Ho, Wo = dy.shape[1:]
+        need_x = ctx.needs_input_grad[0]
+        need_w = ctx.needs_input_grad[1] or dw_slice is not None
+        dx = dw = None
+        if need_x and wt is not None and O % 64 == 0 and I % 8 == 0 and dy.dtype == torch.bfloat16 and min(H, W) > 1:
+            dx = conv3x3_s2_dgrad(dy, wt, H, W, 1, 1)
+            need_x = False
+        if need_w and dw_slice is not None and x.dtype == torch.bfloat16 and (N * Ho * Wo) % 64 == 0 and I % 8 == 0 and O % 8 == 0 and N * H * W < 1 << 31:
+            side_stream_run(lambda: conv3x3_s2_wgrad(dy, x, 1, 1, out=dw_slice), dy, x, dw_slice)
+            need_w = False
+        if need_x or need_w:
+            gx, gw, _ = torch.ops.aten.convolution_backward(dy, x, w, None, (2, 2), (1, 1), (1, 1), False, (0, 0), 1, (need_x, need_w, False))
+            if need_x:
+                dx = gx
+            if need_w:
+                if dw_slice is not None:
+                    dw_slice.view(O, 3, 3, I).add_(gw.permute(0, 2, 3, 1))
+                else:
+                    dw = gw
+        return dx, dw, None, None, None
+
+
+def stem_input_pad3(x, dtype):
+    """fp32 NCHW frames -> the padded 4-slot channels_last image maed_stem7x7s2_* consume, for a 7x7 / stride-2 convolution with ZERO PADDING 3 (torchvision's stem)
+    instead of TF-SAME (stem_input: 2 in front, 3 behind): 3 rows on top, 2 below, 3 columns on either side -- the same (H + 5, W + 6, 4) buffer, the window of
+    output (ho, wo) starting at padded (2 ho, 2 wo) = image (2 ho - 3, 2 wo - 3).  Returns the (N, 4, H + 5, W + 6) channels_last view."""
+    N, C_, H, W = x.shape
+    y = torch.empty(N, H + 5, W + 6, 4, dtype=dtype, device=x.device)
+    check(L.lib().maed_stem_input(_p(x), _p(y), N, C_, H, W, 3, 2, 3, 3, 4, dt_code(dtype), _stream()), "stem_input")
+    return y.permute(0, 3, 1, 2)
