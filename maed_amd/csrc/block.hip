@@ -10,6 +10,7 @@
 //           into the caller's gradient arena), bias gradients fall out of the transposes.
 #include "common.cuh"
 #include "gemm_x3.h"
+#include "gemm_internal.h"
 #include "prof.h"
 #include <hip/hip_runtime.h>
 #include <atomic>
@@ -103,7 +104,6 @@ static SideStream g_side;
 static hipEvent_t g_fence_ring[64];
 static bool g_fence_ok = false;
 static std::once_flag g_runtime_once;
-int maed_sk_init(void);
 int maed_init_runtime(void) {
     std::call_once(g_runtime_once, [] {
         SideStream& ss = g_side;

@@ -12,6 +12,7 @@
 #include "common.cuh"
 #include "gemm_epilogue.cuh"
 #include "gemm_tile.cuh"
+#include "gemm_internal.h"
 #include "gemm_x3.h"
 
 // ------------------------------------------------------------------------------------------------
@@ -373,16 +374,6 @@ static int launch_glds(const void* A, int64_t lda, const void* B, int64_t ldb, i
 #endif
     return MAED_OK;
 }
-
-// csrc/gemm256.hip: 256x256 tiles with the counted-vmcnt LDS-DMA pipeline
-bool maed_gemm_nt_256_launch(int epilogue, const void* A, int64_t lda, const void* B, int64_t ldb, int64_t M, int64_t N, int64_t K, const EpiArgs& e,
-                             hipStream_t s);
-
-// csrc/gemm_sk.hip: persistent K-stream kernel (256x256 tiles, one workgroup per CU, stream-K cuts)
-bool maed_gemm_nt_sk_shape_ok(int64_t M, int64_t N, int64_t K);
-bool maed_gemm_nt_sk_launch(int epilogue, const void* A, int64_t lda, const void* B, int64_t ldb, int64_t M, int64_t N, int64_t K, const EpiArgs& e,
-                            int mode, int grid_opt, hipStream_t s);
-int maed_sk_cus(void);
 
 template <int EPI>
 static int dispatch(const void* A, int64_t lda, const void* B, int64_t ldb, int64_t M, int64_t N, int64_t K, int dtype,

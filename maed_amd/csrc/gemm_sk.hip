@@ -7,8 +7,8 @@
 // traffic; the 256 x 256 pipeline of gemm256.hip halves that traffic but pays a ~2 us prologue and an un-overlapped epilogue per tile
 // (a K = 512 tile is 8 K tiles = ~10 us of main loop), and its grids quantise badly (qkv: 594 tiles = 2.32 waves of 256 CUs; fc2: 198
 // tiles = 0.77).  The vendor library's winners at these shapes are stream-K kernels on 256 x 256 x 64 macro tiles.  Here:
-//   * the main loop IS gemm256.hip's (same LDS images, same four-phase K tile, same counted-vmcnt LDS-DMA ring, waves 4-7 one barrier
-//     behind waves 0-3), but the DMA issue side runs through item boundaries: the first seven half-tiles of the NEXT item are in flight
+//   * the main loop IS gemm256.hip's -- gemm256_pipe.cuh: same LDS images, same four-phase K tile, same counted-vmcnt LDS-DMA ring, waves 4-7 one barrier
+//     behind waves 0-3 -- but the DMA issue side runs through item boundaries: the first seven half-tiles of the NEXT item are in flight
 //     or landed when the current item's last MFMA retires -- no prologue bubble between tiles;
 //   * the epilogue of an item runs between two K tiles of that stream, through LDS the ring does not need at that moment (slot A1 of
 //     buffer 1, whose next DMA is issued in the first phase after the epilogue, for waves 0-3; 16 KB beside the ring for waves 4-7),
@@ -24,19 +24,11 @@
 // Items hold an even number of K tiles (K % 128 == 0, cuts at pair boundaries), so an item always starts in LDS buffer 0.
 #include "common.cuh"
 #include "gemm_epilogue.cuh"
+#include "gemm_internal.h"
+#include "gemm256_pipe.cuh"
 #include <mutex>
 
-#define SK_T 256
-#define SK_BK 64
-#define SK_SLOT (128 * SK_BK)          // elements per half-tile slot (16 KB)
-#define SK_A0 0                        // slot order inside a buffer: consumption order (as gemm256.hip)
-#define SK_B0 1
-#define SK_B1 2
-#define SK_A1 3
-#define SK_RING_ELEMS (2 * 4 * SK_SLOT)             // 128 KB
-#define SK_LDS_ELEMS (SK_RING_ELEMS + 4 * 2048)     // + 16 KB: epilogue staging of waves 4-7
-#define SK_STAGE_BYTE0 (7 * SK_SLOT * 2)            // staging of wave w: byte offset SK_STAGE_BYTE0 + w * 4096 (buffer 1 slot A1, then the extra 16 KB)
-#define SK_SLAB_FLOATS (SK_T * SK_T)                // one partial tile (fp32)
+#define SK_SLAB_FLOATS (P256_T * P256_T)            // one partial tile (fp32)
 #define SK_FULL 0
 #define SK_WRITE 1
 #define SK_FINISH 2
@@ -77,14 +69,6 @@ struct SkWork {
     int tl_hi, tl_lo;          // first / last stream-K tile it touches (relative to dp_tiles)
 };
 struct SkItem { int tile, p0, np, kind; };
-// wave-uniform values the compiler must keep in SGPRs (loop-carried values of the item bookkeeping end up in VGPRs otherwise)
-#define SK_UNI(x_) ((uint32_t)__builtin_amdgcn_readfirstlane((int)(x_)))
-#ifdef MAED_HOSTSIM
-#define SK_OPAQUE(v_) ((void)0)
-#else
-#define SK_OPAQUE(v_) asm volatile("" : "+v"(v_))
-#endif
-
 __device__ __forceinline__ void sk_range(const SkPlan& P, int grid, int g, uint32_t& a, uint32_t& b) {
     const uint32_t skp = (uint32_t)(P.tiles - P.dp_tiles) * (uint32_t)P.kp;       // (grid + 1) * skp < 2^32 (launcher)
     a = ((uint32_t)g * skp) / (uint32_t)grid;
@@ -101,8 +85,8 @@ __device__ __forceinline__ SkWork sk_work(const SkPlan& P, int grid, int g) {
     w.n_sk = has ? w.tl_hi - w.tl_lo + 1 : 0;
     w.has_w = has && (w.sk_b != (uint32_t)(w.tl_hi + 1) * (uint32_t)P.kp);      // its highest tile does not end inside this range: somebody else finishes it
     w.n_items = w.n_dp + w.n_sk;
-    w.n_dp = (int)SK_UNI(w.n_dp); w.n_sk = (int)SK_UNI(w.n_sk); w.n_items = (int)SK_UNI(w.n_items); w.has_w = (int)SK_UNI(w.has_w);
-    w.sk_a = SK_UNI(w.sk_a); w.sk_b = SK_UNI(w.sk_b); w.tl_hi = (int)SK_UNI(w.tl_hi); w.tl_lo = (int)SK_UNI(w.tl_lo);
+    w.n_dp = (int)P256_UNI(w.n_dp); w.n_sk = (int)P256_UNI(w.n_sk); w.n_items = (int)P256_UNI(w.n_items); w.has_w = (int)P256_UNI(w.has_w);
+    w.sk_a = P256_UNI(w.sk_a); w.sk_b = P256_UNI(w.sk_b); w.tl_hi = (int)P256_UNI(w.tl_hi); w.tl_lo = (int)P256_UNI(w.tl_lo);
     return w;
 }
 // item j of the processing order: [the part somebody else finishes] [whole tiles of the data-parallel region] [stream-K tiles, descending: the last one may be
@@ -113,14 +97,14 @@ __device__ __forceinline__ SkItem sk_item(const SkPlan& P, const SkWork& w, int 
     if (w.has_w && j == 0) tl = w.tl_hi;
     else {
         const int jj = j - w.has_w;
-        if (jj < w.n_dp) { it.tile = (int)SK_UNI(w.g + jj * w.grid); it.p0 = 0; it.np = P.kp; it.kind = SK_FULL; return it; }
+        if (jj < w.n_dp) { it.tile = (int)P256_UNI(w.g + jj * w.grid); it.p0 = 0; it.np = P.kp; it.kind = SK_FULL; return it; }
         tl = w.tl_hi - w.has_w - (jj - w.n_dp);
     }
     const uint32_t t0 = (uint32_t)tl * (uint32_t)P.kp, t1 = t0 + (uint32_t)P.kp;
     const uint32_t a = w.sk_a > t0 ? w.sk_a : t0, b = w.sk_b < t1 ? w.sk_b : t1;
     it.tile = P.dp_tiles + tl; it.p0 = (int)(a - t0); it.np = (int)(b - a);
     it.kind = (b != t1) ? SK_WRITE : (a != t0) ? SK_FINISH : SK_FULL;
-    it.tile = (int)SK_UNI(it.tile); it.p0 = (int)SK_UNI(it.p0); it.np = (int)SK_UNI(it.np); it.kind = (int)SK_UNI(it.kind);
+    it.tile = (int)P256_UNI(it.tile); it.p0 = (int)P256_UNI(it.p0); it.np = (int)P256_UNI(it.np); it.kind = (int)P256_UNI(it.kind);
     return it;
 }
 
@@ -128,7 +112,7 @@ template <int EPI>
 __global__ __launch_bounds__(512, 2) void gemm_nt_sk_bf16_kernel(const bf16* __restrict__ A, int64_t lda, const bf16* __restrict__ B, int64_t ldb,
                                                                   int64_t M, int64_t N, int64_t K, SkPlan P, EpiArgs e,
                                                                   float* __restrict__ slabs, uint32_t* __restrict__ flags, uint32_t* fault) {
-    __shared__ __attribute__((aligned(1024))) unsigned short lds_raw[SK_LDS_ELEMS];          // 144 KB
+    __shared__ __attribute__((aligned(1024))) unsigned short lds_raw[P256_LDS_ELEMS];        // 144 KB
     const int tid = threadIdx.x, lane = tid & 63;
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);        // scalar: LDS-DMA bases (M0) and the wave-group branches stay on the SALU
     const int wr = wave >> 2, wc = wave & 3;
@@ -142,7 +126,7 @@ __global__ __launch_bounds__(512, 2) void gemm_nt_sk_bf16_kernel(const bf16* __r
     const SkWork W = sk_work(P, grid, g);
     if (W.n_items == 0) return;
 
-    // ---- staging map (gemm256.hip): a half-tile is 128 rows x 128 B = 1024 chunks of 16 B, two per thread (round i = 0, 1); wave w fills slot rows
+    // ---- staging map (as gemm256.hip): a half-tile is 128 rows x 128 B = 1024 chunks of 16 B, two per thread (round i = 0, 1); wave w fills slot rows
     //      8w + 64i .. +7, lane l the (swizzled) chunk of row 8w + 64i + (l>>3).  Slot row s of A-half q is tile row (s>>6)*128 + q*64 + (s&63);
     //      slot row s of B-half q is tile column (s>>5)*64 + q*32 + (s&31).
     const int r = wave * 8 + (lane >> 3);
@@ -164,91 +148,41 @@ __global__ __launch_bounds__(512, 2) void gemm_nt_sk_bf16_kernel(const bf16* __r
     }
 #define SK_SET_OFFS(tile_)                                                                          \
     {                                                                                               \
-        const int m0__ = ((tile_) / P.tiles_n) * SK_T, n0__ = ((tile_) % P.tiles_n) * SK_T;         \
+        const int m0__ = ((tile_) / P.tiles_n) * P256_T, n0__ = ((tile_) % P.tiles_n) * P256_T;     \
         int r_ = r; uint32_t sc_ = (uint32_t)schunk * 16u;                                          \
-        SK_OPAQUE(r_); SK_OPAQUE(sc_);                                                              \
+        P256_OPAQUE(r_); P256_OPAQUE(sc_);                                                          \
         SK_OFFS(0, m0__, n0__) SK_OFFS(1, m0__, n0__) SK_OFFS(2, m0__, n0__) SK_OFFS(3, m0__, n0__)   \
     }
-    unsigned short* const ldsw = lds_raw + wave * 8 * SK_BK;          // this wave's rows of round 0 inside a slot (scalar)
+    unsigned short* const ldsw = lds_raw + wave * 8 * P256_BK;          // this wave's rows of round 0 inside a slot (scalar)
     const char* const Ab = reinterpret_cast<const char*>(A);
     const char* const Bb = reinterpret_cast<const char*>(B);
     // one LDS-DMA per thread: scalar base (operand + K byte offset) + 32-bit lane offset -> round i_ of slot slot_ of buffer buf_
-#define SK_DMA(base_, kb_, off_, buf_, slot_, i_) MAED_LDS_DMA16((base_) + SK_UNI(kb_), off_, ldsw + ((buf_) * 4 + (slot_)) * SK_SLOT + (i_) * 64 * SK_BK)
-
-    // ---- fragments (gemm256.hip): A rows wr*64 + rt*32 + l31 of slot A[qm], B rows wc*32 + l31 of slot B[qn]; chunk (2*kk + hi) ^ fsw
-    const int fsw = (l31 >> 1) & 7;
-    const char* const ldsb = reinterpret_cast<const char*>(lds_raw);
-    const char* const fa0 = ldsb + (wr * 64 + l31) * (SK_BK * 2) + ((0 + hi) ^ fsw) * 16;
-    const char* const fa1 = ldsb + (wr * 64 + l31) * (SK_BK * 2) + ((2 + hi) ^ fsw) * 16;
-    const char* const fa2 = ldsb + (wr * 64 + l31) * (SK_BK * 2) + ((4 + hi) ^ fsw) * 16;
-    const char* const fa3 = ldsb + (wr * 64 + l31) * (SK_BK * 2) + ((6 + hi) ^ fsw) * 16;
-    const char* const fb0 = ldsb + (wc * 32 + l31) * (SK_BK * 2) + ((0 + hi) ^ fsw) * 16;
-    const char* const fb1 = ldsb + (wc * 32 + l31) * (SK_BK * 2) + ((2 + hi) ^ fsw) * 16;
-    const char* const fb2 = ldsb + (wc * 32 + l31) * (SK_BK * 2) + ((4 + hi) ^ fsw) * 16;
-    const char* const fb3 = ldsb + (wc * 32 + l31) * (SK_BK * 2) + ((6 + hi) ^ fsw) * 16;
-    bf16x8_t a00, a01, a02, a03, a10, a11, a12, a13;            // a[rt][kk]   (named scalars: never demoted to scratch)
-    bf16x8_t b00, b01, b02, b03, b10, b11, b12, b13;            // b[qn][kk]
-    f32x16_t c000, c001, c010, c011, c100, c101, c110, c111;    // c[qm][rt][qn]
-#define SK_ZERO_ACC()                                                                               \
-    _Pragma("unroll") for (int x = 0; x < 16; ++x) { c000[x] = 0.f; c001[x] = 0.f; c010[x] = 0.f; c011[x] = 0.f; c100[x] = 0.f; c101[x] = 0.f; c110[x] = 0.f; c111[x] = 0.f; }
-    SK_ZERO_ACC()
-#define SK_FRAG(base_, buf_, slot_, rowoff_) (*reinterpret_cast<const bf16x8_t*>((base_) + (((buf_) * 4 + (slot_)) * SK_SLOT + (rowoff_) * SK_BK) * 2))
-#define SK_READ_A(buf_, slot_)                                                                                              \
-    a00 = SK_FRAG(fa0, buf_, slot_, 0); a01 = SK_FRAG(fa1, buf_, slot_, 0); a02 = SK_FRAG(fa2, buf_, slot_, 0); a03 = SK_FRAG(fa3, buf_, slot_, 0); \
-    a10 = SK_FRAG(fa0, buf_, slot_, 32); a11 = SK_FRAG(fa1, buf_, slot_, 32); a12 = SK_FRAG(fa2, buf_, slot_, 32); a13 = SK_FRAG(fa3, buf_, slot_, 32);
-#define SK_READ_B0(buf_) b00 = SK_FRAG(fb0, buf_, SK_B0, 0); b01 = SK_FRAG(fb1, buf_, SK_B0, 0); b02 = SK_FRAG(fb2, buf_, SK_B0, 0); b03 = SK_FRAG(fb3, buf_, SK_B0, 0);
-#define SK_READ_B1(buf_) b10 = SK_FRAG(fb0, buf_, SK_B1, 0); b11 = SK_FRAG(fb1, buf_, SK_B1, 0); b12 = SK_FRAG(fb2, buf_, SK_B1, 0); b13 = SK_FRAG(fb3, buf_, SK_B1, 0);
-    // one phase (gemm256.hip): fragment reads ; barrier ; fragments landed ; 8 MFMAs (transposed tiles: first operand = weight rows, a lane owns one output ROW)
-    // at raised priority with the phase's two LDS-DMA instructions in their shadow ; counted wait ; barrier
-#define SK_PHASE(READS_, ISSUE0_, ISSUE1_, WAIT_, c0_, c1_, bq_)                                     \
-    READS_                                                                                          \
-    __builtin_amdgcn_s_barrier();                                                                   \
-    MAED_WAIT_LGKMCNT0();                                                                           \
-    __builtin_amdgcn_sched_barrier(0);                                                              \
-    __builtin_amdgcn_s_setprio(1);                                                                  \
-    c0_ = __builtin_amdgcn_mfma_f32_32x32x16_bf16(bq_##0, a00, c0_, 0, 0, 0);                       \
-    c1_ = __builtin_amdgcn_mfma_f32_32x32x16_bf16(bq_##0, a10, c1_, 0, 0, 0);                       \
-    __builtin_amdgcn_sched_barrier(0);                                                              \
-    ISSUE0_;                                                                                        \
-    __builtin_amdgcn_sched_barrier(0);                                                              \
-    c0_ = __builtin_amdgcn_mfma_f32_32x32x16_bf16(bq_##1, a01, c0_, 0, 0, 0);                       \
-    c1_ = __builtin_amdgcn_mfma_f32_32x32x16_bf16(bq_##1, a11, c1_, 0, 0, 0);                       \
-    c0_ = __builtin_amdgcn_mfma_f32_32x32x16_bf16(bq_##2, a02, c0_, 0, 0, 0);                       \
-    __builtin_amdgcn_sched_barrier(0);                                                              \
-    ISSUE1_;                                                                                        \
-    __builtin_amdgcn_sched_barrier(0);                                                              \
-    c1_ = __builtin_amdgcn_mfma_f32_32x32x16_bf16(bq_##2, a12, c1_, 0, 0, 0);                       \
-    c0_ = __builtin_amdgcn_mfma_f32_32x32x16_bf16(bq_##3, a03, c0_, 0, 0, 0);                       \
-    c1_ = __builtin_amdgcn_mfma_f32_32x32x16_bf16(bq_##3, a13, c1_, 0, 0, 0);                       \
-    __builtin_amdgcn_s_setprio(0);                                                                  \
-    WAIT_;                                                                                          \
-    __builtin_amdgcn_s_barrier();
-#define SK_NONE ((void)0)
-    // K-tile pair (t, t+1) of the stream, t in buffer 0.  Issue order = consumption order, six to seven phases ahead of the read (gemm256.hip):
-    //   even tile  q1: A1(t+1) [pending: pa1 / pa3 at kpa]   q2..q4: A0, B0, B1 of tile t+2 [issue context at kb_nx]
-    //   odd tile   q1: A1(t+2)                               q2..q4: A0, B0, B1 of tile t+3 [kb_nx + one K tile]
-    // Every phase ends with vmcnt(8): the half-tile issued four phases ago has landed; it is read two phases later at the earliest.
-    // EVENWAIT_: the wait of the even tile's four phases -- nothing for the FIRST pair of an item: whatever was issued before the item boundary has landed
-    // (the prologue, the epilogue and the slab hand-over begin with vmcnt(0)), so the stream runs five phases (~2 us) before the first counted wait, which, VMEM
-    // operations retiring in order, is also the first that has to see the epilogue's global stores acknowledged
-#define SK_PAIR(EVENWAIT_)                                                                                                                                 \
-    {                                                                                                                                                     \
-        const uint32_t kb1__ = SK_UNI(kb_nx + SK_BK * 2);                                                                                                 \
-        SK_PHASE(SK_READ_A(0, SK_A0) SK_READ_B0(0), SK_DMA(Ab, kpa, pa1, 1, SK_A1, 0), SK_DMA(Ab, kpa, pa3, 1, SK_A1, 1), EVENWAIT_, c000, c010, b0) \
-        SK_PHASE(SK_READ_B1(0), SK_DMA(Ab, kb_nx, ao0, 0, SK_A0, 0), SK_DMA(Ab, kb_nx, ao2, 0, SK_A0, 1), EVENWAIT_, c001, c011, b1)              \
-        SK_PHASE(SK_READ_A(0, SK_A1), SK_DMA(Bb, kb_nx, bo0, 0, SK_B0, 0), SK_DMA(Bb, kb_nx, bo2, 0, SK_B0, 1), EVENWAIT_, c101, c111, b1)        \
-        SK_PHASE(, SK_DMA(Bb, kb_nx, bo1, 0, SK_B1, 0), SK_DMA(Bb, kb_nx, bo3, 0, SK_B1, 1), EVENWAIT_, c100, c110, b0)                           \
-        SK_PHASE(SK_READ_A(1, SK_A0) SK_READ_B0(1), SK_DMA(Ab, kb_nx, ao1, 0, SK_A1, 0), SK_DMA(Ab, kb_nx, ao3, 0, SK_A1, 1), MAED_WAIT_VMCNT(8), c000, c010, b0) \
-        SK_PHASE(SK_READ_B1(1), SK_DMA(Ab, kb1__, ao0, 1, SK_A0, 0), SK_DMA(Ab, kb1__, ao2, 1, SK_A0, 1), MAED_WAIT_VMCNT(8), c001, c011, b1)              \
-        SK_PHASE(SK_READ_A(1, SK_A1), SK_DMA(Bb, kb1__, bo0, 1, SK_B0, 0), SK_DMA(Bb, kb1__, bo2, 1, SK_B0, 1), MAED_WAIT_VMCNT(8), c101, c111, b1)        \
-        SK_PHASE(, SK_DMA(Bb, kb1__, bo1, 1, SK_B1, 0), SK_DMA(Bb, kb1__, bo3, 1, SK_B1, 1), MAED_WAIT_VMCNT(8), c100, c110, b0)                           \
-        pa1 = ao1; pa3 = ao3; kpa = kb1__;                                                                                                                \
+#define SK_DMA(base_, kb_, off_, buf_, slot_, i_) MAED_LDS_DMA16((base_) + P256_UNI(kb_), off_, ldsw + ((buf_) * 4 + (slot_)) * P256_SLOT + (i_) * 64 * P256_BK)
+#define P256_DMA_A(kb_, off_, buf_, slot_, i_) SK_DMA(Ab, kb_, off_, buf_, slot_, i_)
+#define P256_DMA_B(kb_, off_, buf_, slot_, i_) SK_DMA(Bb, kb_, off_, buf_, slot_, i_)
+#define P256_PA1 pa1
+#define P256_PA3 pa3
+#define P256_READ_A P256_NT_READ_A
+#define P256_READ_B0 P256_NT_READ_B0
+#define P256_READ_B1 P256_NT_READ_B1
+    P256_NT_FRAG_BASES()
+    P256_DECLARE_REGS()
+    P256_ZERO_ACC()
+    // K-tile pair (t, t+1) of the stream (gemm256_pipe.cuh): the pending A1 half [pa1 / pa3 at kpa], then the issue context [ao / bo at kb_nx, + one K tile].
+    // EVENWAIT_: nothing for the FIRST pair of an item: whatever was issued before the item boundary has landed (the prologue, the epilogue and the slab hand-over
+    // begin with vmcnt(0)), so the stream runs five phases (~2 us) before the first counted wait, which, VMEM operations retiring in order, is also the first that
+    // has to see the epilogue's global stores acknowledged
+#define SK_PAIR(EVENWAIT_)                                                                          \
+    {                                                                                               \
+        const uint32_t kb1__ = P256_UNI(kb_nx + P256_BK * 2);                                       \
+        P256_PAIR(EVENWAIT_, kpa, kb_nx, kb1__)                                                     \
+        pa1 = ao1; pa3 = ao3; kpa = kb1__;                                                          \
     }
     // ---- the issue side: (item, pair) of the next K-tile pair to copy
     int ij = 0;                                        // item the issue side is in
     SkItem iti = sk_item(P, W, 0);
     int left_i = iti.np;                               // pairs of that item not yet issued
-    uint32_t kb_nx = SK_UNI((uint32_t)iti.p0 * (2 * SK_BK * 2));   // K byte offset of the pair to issue next (kept scalar: the DMA's base is an SGPR pair)
+    uint32_t kb_nx = P256_UNI((uint32_t)iti.p0 * (2 * P256_BK * 2));   // K byte offset of the pair to issue next (kept scalar: the DMA's base is an SGPR pair)
     uint32_t kpa;
     SK_SET_OFFS(iti.tile)
     // advance by one pair: inside the item, or into the next item (new operand offsets).  Past the end of this workgroup's stream the issue side stays where it
@@ -256,24 +190,18 @@ __global__ __launch_bounds__(512, 2) void gemm_nt_sk_bf16_kernel(const bf16* __r
     // which keeps EVERY pair of the stream on the one steady-state code path: no drain variant, no second path that writes the accumulators
 #define SK_ADVANCE()                                                                                \
     {                                                                                               \
-        if (left_i > 1) { --left_i; kb_nx = SK_UNI(kb_nx + 2 * SK_BK * 2); }                        \
+        if (left_i > 1) { --left_i; kb_nx = P256_UNI(kb_nx + 2 * P256_BK * 2); }                    \
         else if (ij + 1 < W.n_items) {                                                              \
             ++ij;                                                                                   \
             iti = sk_item(P, W, ij);                                                                \
-            left_i = iti.np; kb_nx = SK_UNI((uint32_t)iti.p0 * (2 * SK_BK * 2));                    \
+            left_i = iti.np; kb_nx = P256_UNI((uint32_t)iti.p0 * (2 * P256_BK * 2));                \
             SK_SET_OFFS(iti.tile)                                                                   \
         }                                                                                           \
     }
     // ---- prologue: the first pair except the A1 half of its odd tile (the issue order of the steady state); A0, B0, B1 of its even tile must have landed
     {
-        const uint32_t kb1 = SK_UNI(kb_nx + SK_BK * 2);
-        SK_DMA(Ab, kb_nx, ao0, 0, SK_A0, 0); SK_DMA(Ab, kb_nx, ao2, 0, SK_A0, 1);
-        SK_DMA(Bb, kb_nx, bo0, 0, SK_B0, 0); SK_DMA(Bb, kb_nx, bo2, 0, SK_B0, 1);
-        SK_DMA(Bb, kb_nx, bo1, 0, SK_B1, 0); SK_DMA(Bb, kb_nx, bo3, 0, SK_B1, 1);
-        SK_DMA(Ab, kb_nx, ao1, 0, SK_A1, 0); SK_DMA(Ab, kb_nx, ao3, 0, SK_A1, 1);
-        SK_DMA(Ab, kb1, ao0, 1, SK_A0, 0); SK_DMA(Ab, kb1, ao2, 1, SK_A0, 1);
-        SK_DMA(Bb, kb1, bo0, 1, SK_B0, 0); SK_DMA(Bb, kb1, bo2, 1, SK_B0, 1);
-        SK_DMA(Bb, kb1, bo1, 1, SK_B1, 0); SK_DMA(Bb, kb1, bo3, 1, SK_B1, 1);
+        const uint32_t kb1 = P256_UNI(kb_nx + P256_BK * 2);
+        P256_PROLOGUE(kb_nx, kb1)
         pa1 = ao1; pa3 = ao3; kpa = kb1;
     }
     SK_ADVANCE()
@@ -282,14 +210,14 @@ __global__ __launch_bounds__(512, 2) void gemm_nt_sk_bf16_kernel(const bf16* __r
     if (wr == 1) __builtin_amdgcn_s_barrier();        // waves 4-7 run one barrier behind (wave-uniform branch)
 
     constexpr bool vec_ok = true;       // launcher: N, ldo, ldaux multiples of 8, 16-byte aligned outputs -- the scalar tails of gemm_epilogue.cuh are not instantiated here
-    char* const stg = reinterpret_cast<char*>(lds_raw) + SK_STAGE_BYTE0 + wave * 4096;          // 16 rows x 256 B, 16-byte chunk c of row r at slot c ^ r
+    char* const stg = reinterpret_cast<char*>(lds_raw) + P256_STAGE_BYTE0 + wave * 4096;          // 16 rows x 256 B, 16-byte chunk c of row r at slot c ^ r
     const int r16 = l31 & 15, rhalf = l31 >> 4;
     const int rr = lane >> 3, c8 = lane & 7;
     float* const slab = slabs + (int64_t)g * SK_SLAB_FLOATS;
 
     for (int j = 0; j < W.n_items; ++j) {
         const SkItem it = sk_item(P, W, j);
-        SK_PAIR(SK_NONE)
+        SK_PAIR(P256_NONE)
         SK_ADVANCE()
         for (int p = 1; p < it.np; ++p) {
             SK_PAIR(MAED_WAIT_VMCNT(8))
@@ -300,7 +228,7 @@ __global__ __launch_bounds__(512, 2) void gemm_nt_sk_bf16_kernel(const bf16* __r
         // the lane indices of the boundary code, made opaque once per item: everything derived from them (32 row offsets times the leading dimension, 32 slab
         // addresses, the staging addresses) would otherwise be hoisted out of the item loop and live -- spilled -- across the K stream
         int rr_l = rr, c8_l = c8, tid_l = tid, r16_l = r16;
-        SK_OPAQUE(rr_l); SK_OPAQUE(c8_l); SK_OPAQUE(tid_l); SK_OPAQUE(r16_l);
+        P256_OPAQUE(rr_l); P256_OPAQUE(c8_l); P256_OPAQUE(tid_l); P256_OPAQUE(r16_l);
 
         // ---- the last part of a tile cut along K (always this workgroup's last item): add the slabs of the workgroups below that
         //      hold its other parts, nearest first.  (One loop for both kinds of item -- no slabs for a whole tile: accumulators that one branch modifies and
@@ -333,7 +261,7 @@ __global__ __launch_bounds__(512, 2) void gemm_nt_sk_bf16_kernel(const bf16* __r
                 sk_acquire();
             }
             __syncthreads();
-            npart = (int)SK_UNI(npart);
+            npart = (int)P256_UNI(npart);
         }
         for (int gp = g - 1, seen = 0; seen < npart; --gp) {
             uint32_t pa_, pb_;
@@ -377,7 +305,7 @@ __global__ __launch_bounds__(512, 2) void gemm_nt_sk_bf16_kernel(const bf16* __r
         } else {
             // ---- epilogue: per (qm, rt) and row half a 16 x 64 fp32 piece of the wave's tile through its private staging area (lanes of the half write their
             //      eight float4, all lanes read full row segments back: 8 lanes cover 64 columns = one 128-byte line of bf16)
-            const int64_t m0 = (int64_t)(it.tile / P.tiles_n) * SK_T, n0 = (int64_t)(it.tile % P.tiles_n) * SK_T;
+            const int64_t m0 = (int64_t)(it.tile / P.tiles_n) * P256_T, n0 = (int64_t)(it.tile % P.tiles_n) * P256_T;
             // Per (qm, rt): the operand the epilogue reads from memory (fp32 residual / bf16 pre-activation) for the piece's four row groups first -- one load latency
             // per 32 x 64 piece instead of one per row group, and they overlap the staging traffic -- then the two row halves through the staging area.
             constexpr bool kAux = EPI == MAED_EPI_RESID_F32 || EPI == MAED_EPI_MUL_DGELU;
@@ -394,8 +322,7 @@ __global__ __launch_bounds__(512, 2) void gemm_nt_sk_bf16_kernel(const bf16* __r
             {                                                                                                               \
                 const int lr = (ps_) * 8 + rr_l;                                                                            \
                 const int64_t row = SK_ROW(qm_, rt_, h_, ps_);                                                              \
-                const float4 u0 = *reinterpret_cast<const float4*>(stg + lr * 256 + (((2 * c8_l) ^ lr) << 4));              \
-                const float4 u1 = *reinterpret_cast<const float4*>(stg + lr * 256 + (((2 * c8_l + 1) ^ lr) << 4));          \
+                P256_STAGE_READ8(u0, u1, stg, lr, c8_l)                                                                     \
                 float v8[8] = {u0.x, u0.y, u0.z, u0.w, u1.x, u1.y, u1.z, u1.w};                                             \
                 if (kAux && hx##h_##ps_) {                                                                                  \
                     if constexpr (EPI == MAED_EPI_RESID_F32) {                                                              \
@@ -410,14 +337,7 @@ __global__ __launch_bounds__(512, 2) void gemm_nt_sk_bf16_kernel(const bf16* __r
                 } else if (!kAux && row < M && c0 < N) epilogue_store8<EPI, bf16>(e, row, c0, N, v8, vec_ok);               \
             }
 #define SK_STORE_HALF(accA_, accB_, qm_, rt_, h_)                                                                           \
-            MAED_WAVE_LDS_SYNC();                                                                                           \
-            if (rhalf == (h_)) {                                                                                            \
-                _Pragma("unroll") for (int q4 = 0; q4 < 4; ++q4) {                                                          \
-                    *reinterpret_cast<float4*>(stg + r16_l * 256 + (((2 * q4 + hi) ^ r16_l) << 4)) = make_float4(accA_[4 * q4], accA_[4 * q4 + 1], accA_[4 * q4 + 2], accA_[4 * q4 + 3]);      \
-                    *reinterpret_cast<float4*>(stg + r16_l * 256 + (((8 + 2 * q4 + hi) ^ r16_l) << 4)) = make_float4(accB_[4 * q4], accB_[4 * q4 + 1], accB_[4 * q4 + 2], accB_[4 * q4 + 3]);  \
-                }                                                                                                           \
-            }                                                                                                               \
-            MAED_WAVE_LDS_SYNC();                                                                                           \
+            P256_STAGE_WRITE_HALF(accA_, accB_, h_, stg, r16_l)                                                             \
             SK_APPLY(qm_, rt_, h_, 0) SK_APPLY(qm_, rt_, h_, 1)
 #define SK_STORE_PIECE(accA_, accB_, qm_, rt_)                                                                              \
             {                                                                                                               \
@@ -438,7 +358,7 @@ __global__ __launch_bounds__(512, 2) void gemm_nt_sk_bf16_kernel(const bf16* __r
 #undef SK_ROW
             MAED_WAVE_LDS_SYNC();
         }
-        SK_ZERO_ACC()
+        P256_ZERO_ACC()
     }
     MAED_WAIT_VMCNT0();        // the re-issued copies of the stream's last pair must have landed before this workgroup's LDS is handed to the next one
 }
@@ -535,7 +455,7 @@ bool maed_gemm_nt_sk_launch(int epilogue, const void* A, int64_t lda, const void
     // per-tile kernels at the K = 512 ... 2048 shapes of cfg3 (one workgroup per CU cannot hide an item's epilogue stores behind another workgroup's MFMAs)
     if (mode == 1 && K < 2560) return false;
     if (!g_sk.base && maed_sk_init() != MAED_OK) return false;
-    const int tm = (int)((M + SK_T - 1) / SK_T), tn = (int)((N + SK_T - 1) / SK_T);
+    const int tm = (int)((M + P256_T - 1) / P256_T), tn = (int)((N + P256_T - 1) / P256_T);
     const int64_t T = (int64_t)tm * tn;
     if (T > (1 << 24)) return false;
     int G = grid_opt > 0 ? grid_opt : g_sk.ncu;

@@ -12,6 +12,7 @@
 #include "common.cuh"
 #include "gemm_epilogue.cuh"      // xcd_remap
 #include "gemm_x3.h"
+#include "gemm_internal.h"
 #include "prof.h"
 #include <stdlib.h>
 
@@ -28,11 +29,6 @@ int maed_tn_splits(int tiles) {
 }
 static int tn_remap() { return 1; }     // XCD-aware (split, tile) order: -6...8 % and 292 -> 189 MB of HBM traffic per launch (profiles/r02_pmc)
 
-bool maed_gemm_tn_sk_ok(int64_t M, int N, int K, int64_t ldy, int64_t ldx, int64_t ldw, const void* Y, const void* X, const void* dW);      // gemm_tn_sk.hip
-int maed_gemm_tn_sk_launch(const void* Y, int64_t ldy, const void* X, int64_t ldx, int64_t M, int N, int K, float* dW, int64_t ldw, float* dbias, int grid_opt, hipStream_t s);
-int maed_sk_cus(void);                                                                                                          // gemm_sk.hip
-bool maed_gemm_tn_dma_ok(int64_t M, int N, int K, int64_t ldy, int64_t ldx);                                            // gemm_tn2.hip
-int maed_gemm_tn_dma_launch(const void* Y, int64_t ldy, const void* X, int64_t ldx, int64_t M, int N, int K, float* dW, int64_t ldw, float* dbias, int which, hipStream_t stream);
 bool maed_conv3x3_wgrad_rows64_ok(int F, int H, int W, int Cin, int Cout);                                            // conv3x3_rows.hip
 int maed_conv3x3_wgrad_rows64_launch(const void* dy, const void* x, float* dW, void* scratch, int F, int H, int W, hipStream_t stream);
 

@@ -13,6 +13,7 @@
 // Bias gradient: column sums of Y as one more MFMA against a ones operand in the workgroups that own them (no VALU pass over the tile).
 #include "common.cuh"
 #include "gemm_epilogue.cuh"      // xcd_remap
+#include "gemm_internal.h"
 #include "prof.h"
 
 #define T2_BM 32                          // reduction rows per stage
