@@ -488,6 +488,21 @@ int maed_gn_affine_grad_batch(const maed_gn_affine_item* items, int count, void*
  * ceil(W/2),C) and the winning tap per output element (idx, uint8, same shape as y; ATen tie/NaN rule); backward gathers dx. */
 int maed_maxpool3s2_same_fwd(const void* x, void* y, uint8_t* idx, int N, int H, int W, int C, int dtype, void* stream);
 int maed_maxpool3s2_same_bwd(const void* dy, const uint8_t* idx, void* dx, int N, int H, int W, int C, int dtype, void* stream);
+/* The stem's GroupNorm(32) + ReLU + MaxPool2dSame(3, 2) in ONE pass (resnetv2.py:35-49,61-72,282-292): x (N,H,W,C) is the RAW stem convolution output, sums its
+ * (N,32,2) statistics (sums_zeroed as maed_groupnorm_fwd: 2 = the stem convolution's epilogue left them).  Every tap is normalised as maed_groupnorm_fwd(relu = 1)
+ * does, ROUNDED to `dtype`, and only then compared: y and idx are bit for bit what maed_groupnorm_fwd followed by maed_maxpool3s2_same_fwd give, without the
+ * full-resolution normalised tensor (one write and one read of N*H*W*C elements less).  Backward: maed_maxpool3s2_same_bwd with idx, then maed_groupnorm_bwd on x
+ * (relu = 1, no mask: recomputed from x). */
+int maed_gn_relu_maxpool3s2_fwd(const void* x, const float* gamma, const float* beta, void* y, uint8_t* idx, double* sums, int N, int H, int W, int C, float eps,
+                                int dtype, int sums_zeroed, void* stream);
+/* The closing GroupNorm of a bottleneck with a downsample shortcut (resnetv2.py:189-216): y = relu(GN(x) * gamma + beta + r), r = GN2(res) * gamma2 + beta2
+ * ROUNDED to `dtype` -- bit for bit maed_groupnorm_fwd(res, relu = 0) followed by maed_groupnorm_fwd(x, residual = that, relu = 1), without the normalised
+ * shortcut tensor.  res: the RAW shortcut convolution output, same shape as x; sums / sums2, sums_zeroed / sums2_zeroed, relu_mask as maed_groupnorm_fwd.
+ * Backward: two maed_groupnorm_bwd calls with the same dy and relu_mask, relu = 1, dres = NULL -- on (x, sums, gamma, beta) and on (res, sums2, gamma2, beta2):
+ * the shortcut's gradient (dy masked by the ReLU bits) is never materialised. */
+int maed_groupnorm_dual_fwd(const void* x, const float* gamma, const float* beta, double* sums, const void* res, const float* gamma2, const float* beta2,
+                            double* sums2, void* y, uint8_t* relu_mask, int N, int HW, int C, float eps, float eps2, int dtype, int sums_zeroed,
+                            int sums2_zeroed, void* stream);
 
 /* Input of the stem convolution in one pass: x fp32 (N,C,H,W) contiguous -> y (N, H + pad_top + pad_bottom, W + pad_left + pad_right, c_stride) channels_last in
  * the compute dtype, zero borders (the TF-SAME padding of resnetv2.py:51-59 materialised), channel slots C .. c_stride-1 zero.  C <= c_stride <= 4

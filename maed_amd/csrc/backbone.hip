@@ -232,6 +232,8 @@ __global__ __launch_bounds__(256) void gn_apply_kernel(const T* __restrict__ x, 
                                                        const float* __restrict__ gamma, const float* __restrict__ beta, T* __restrict__ y,
                                                        uint8_t* __restrict__ mask, int HW, int C, float eps, int rows_per_wg,
                                                        bf16* __restrict__ twin_x = nullptr, bf16* __restrict__ twin_y = nullptr) {
+    // (the moments and the a / b below are repeated in gn_group_moments / gn_affine8 for gn_apply_dual_kernel and gn_relu_maxpool3s2_fwd_kernel, whose results must
+    //  be THIS kernel's bits: an edit here goes there too)
     // twin_x / twin_y (maed_groupnorm_fwd_twin, T = float): bf16 copies of the input and of the result for a bf16 backward, written from the registers of this pass
     __shared__ float lmu[GN_G], lrs[GN_G];
     const int n = blockIdx.y;
@@ -276,6 +278,70 @@ __global__ __launch_bounds__(256) void gn_apply_kernel(const T* __restrict__ x, 
             for (int j = 0; j < 8; ++j) o[j] = fmaxf(o[j], 0.f); }
         st8(y + base + (int64_t)r * C, o);
         if (twin_y) st8_nt(twin_y + base + (int64_t)r * C, o);
+    }
+}
+
+// (mean, rstd) of the 32 groups of frame n from its statistics, as gn_apply_kernel computes them; threads 0..31 of the workgroup, barrier at the caller
+__device__ __forceinline__ void gn_group_moments(const double* __restrict__ sums, int n, int HW, int C, float eps, float* lmu, float* lrs) {
+    const double cnt = (double)HW * (C / GN_G);
+    const double m = sums[((int64_t)n * GN_G + threadIdx.x) * 2] / cnt;
+    double var = sums[((int64_t)n * GN_G + threadIdx.x) * 2 + 1] / cnt - m * m;
+    if (var < 0.0) var = 0.0;
+    lmu[threadIdx.x] = (float)m; lrs[threadIdx.x] = (float)(1.0 / sqrt(var + (double)eps));
+}
+// y = x*a + b of the 8 channels behind channel block cb, as gn_apply_kernel computes them
+__device__ __forceinline__ void gn_affine8(const float* __restrict__ gamma, const float* __restrict__ beta, const float* lmu, const float* lrs, int cb, int cpg,
+                                           float (&a)[8], float (&b)[8]) {
+    float gg[8], bb[8];
+    ld8(gamma + cb * 8, gg); ld8(beta + cb * 8, bb);
+#pragma unroll
+    for (int j = 0; j < 8; ++j) {
+        const int g = (cb * 8 + j) / cpg;
+        a[j] = lrs[g] * gg[j]; b[j] = bb[j] - lmu[g] * a[j];
+    }
+}
+
+// ---- forward pass 2 of a block's closing norm whose shortcut is a normalised convolution (downsample blocks): the shortcut's affine is applied HERE ----------
+// y = relu(GN(x) + round_T(GN2(res))): res is the RAW shortcut convolution output.  The rounding of the shortcut term to the storage type is what the two-kernel
+// path (gn_apply_kernel<T,false,false> writing the normalised shortcut, gn_apply_kernel<T,true,true> reading it) does by storing it: the same bits, one
+// full-size write and one launch less.
+template <typename T>
+__global__ __launch_bounds__(256) void gn_apply_dual_kernel(const T* __restrict__ x, const double* __restrict__ sums, const float* __restrict__ gamma,
+                                                            const float* __restrict__ beta, const T* __restrict__ res, const double* __restrict__ sums2,
+                                                            const float* __restrict__ gamma2, const float* __restrict__ beta2, T* __restrict__ y,
+                                                            uint8_t* __restrict__ mask, int HW, int C, float eps, float eps2, int rows_per_wg) {
+    __shared__ float lmu[GN_G], lrs[GN_G], lmu2[GN_G], lrs2[GN_G];
+    const int n = blockIdx.y;
+    if (threadIdx.x < GN_G) {
+        gn_group_moments(sums, n, HW, C, eps, lmu, lrs);
+        gn_group_moments(sums2, n, HW, C, eps2, lmu2, lrs2);
+    }
+    __syncthreads();
+    const int cbn = C / 8, cb = threadIdx.x % cbn, rsub = threadIdx.x / cbn, rstep = 256 / cbn, cpg = C / GN_G;
+    float a[8], b[8], a2[8], b2[8];
+    gn_affine8(gamma, beta, lmu, lrs, cb, cpg, a, b);
+    gn_affine8(gamma2, beta2, lmu2, lrs2, cb, cpg, a2, b2);
+    const int r0 = blockIdx.x * rows_per_wg, r1 = min(HW, r0 + rows_per_wg);
+    const int64_t base = ((int64_t)n * HW) * C + cb * 8;
+    for (int r = r0 + rsub; r < r1; r += rstep) {
+        float v[8], rr[8], o[8];
+        gn_load8(x + base + (int64_t)r * C, v);
+        gn_load8(res + base + (int64_t)r * C, rr);
+#pragma unroll
+        for (int j = 0; j < 8; ++j) {
+            const float sh = round_to<T>(fmaf(rr[j], a2[j], b2[j]));
+            o[j] = fmaf(v[j], a[j], b[j]);
+            o[j] += sh;
+        }
+        if (mask) {
+            uint32_t bits = 0;
+#pragma unroll
+            for (int j = 0; j < 8; ++j) bits |= (o[j] > 0.f ? 1u : 0u) << j;
+            mask[((int64_t)n * HW + r) * cbn + cb] = (uint8_t)bits;
+        }
+#pragma unroll
+        for (int j = 0; j < 8; ++j) o[j] = fmaxf(o[j], 0.f);
+        st8(y + base + (int64_t)r * C, o);
     }
 }
 
@@ -675,6 +741,34 @@ extern "C" int maed_groupnorm_fwd_twin(const void* x, const void* residual, cons
     return groupnorm_fwd(x, residual, gamma, beta, y, sums, relu_mask, N, HW, C, eps, relu, MAED_F32, sums_zeroed, twin_x, twin_y, stream);
 }
 
+// the statistics of x into `sums` unless they are there already (sums_zeroed as maed_groupnorm_fwd: 0 = zero them first, 1 = zero already, 2 = statistics present)
+static int gn_stats_if_needed(const void* x, double* sums, int N, int HW, int C, int dtype, int sums_zeroed, hipStream_t s, const char* who) {
+    if (sums_zeroed == 2) return MAED_OK;
+    const int rows = gn_rows_per_wg(N, HW, C);
+    dim3 grid((HW + rows - 1) / rows, N);
+    if (!sums_zeroed) MAED_HIP(hipMemsetAsync(sums, 0, (size_t)N * GN_G * 2 * sizeof(double), s), "groupnorm statistics: memset");
+    MAED_DISPATCH_DTYPE(dtype, T, hipLaunchKernelGGL((gn_stats_kernel<T>), grid, dim3(256), 0, s, (const T*)x, sums, HW, C, rows));
+    MAED_CHECK_LAUNCH(who);
+    return MAED_OK;
+}
+
+extern "C" int maed_groupnorm_dual_fwd(const void* x, const float* gamma, const float* beta, double* sums, const void* res, const float* gamma2, const float* beta2,
+                                       double* sums2, void* y, uint8_t* relu_mask, int N, int HW, int C, float eps, float eps2, int dtype, int sums_zeroed,
+                                       int sums2_zeroed, void* stream) {
+    MAED_CHECK_ARG(x && gamma && beta && sums && res && gamma2 && beta2 && sums2 && y, MAED_ERR_ARG, "groupnorm_dual_fwd: null pointer");
+    MAED_PROPAGATE(gn_check(C, HW, "groupnorm_dual_fwd"));
+    if (N <= 0) return MAED_OK;
+    hipStream_t s = (hipStream_t)stream;
+    MAED_PROPAGATE(gn_stats_if_needed(x, sums, N, HW, C, dtype, sums_zeroed, s, "groupnorm_dual_fwd"));
+    MAED_PROPAGATE(gn_stats_if_needed(res, sums2, N, HW, C, dtype, sums2_zeroed, s, "groupnorm_dual_fwd"));
+    const int rows = gn_rows_per_wg(N, HW, C);
+    dim3 grid((HW + rows - 1) / rows, N);
+    MAED_DISPATCH_DTYPE(dtype, T, hipLaunchKernelGGL((gn_apply_dual_kernel<T>), grid, dim3(256), 0, s, (const T*)x, sums, gamma, beta, (const T*)res, sums2, gamma2,
+                                                      beta2, (T*)y, relu_mask, HW, C, eps, eps2, rows));
+    MAED_CHECK_LAUNCH("groupnorm_dual_fwd");
+    return MAED_OK;
+}
+
 extern "C" int maed_groupnorm_bwd(const void* x, const uint8_t* relu_mask, const void* dy, const double* sums, const float* gamma, const float* beta,
                                   void* dx, void* dres, float* dgamma, float* dbeta, float* ab_scratch, int N, int HW, int C, float eps,
                                   int relu, int dtype, int ab_zeroed, uint32_t* frame_sync, void* aux_stream, void* stream) {
@@ -798,6 +892,52 @@ __global__ __launch_bounds__(256) void maxpool3s2_fwd_kernel(const T* __restrict
     *reinterpret_cast<uint2*>(idx + i * 8) = make_uint2(lo, hi);
 }
 
+// The stem's GroupNorm + ReLU folded into the pool (maed_gn_relu_maxpool3s2_fwd): x is the RAW convolution output, every tap is normalised on the fly exactly as
+// gn_apply_kernel<T,false,true> would have stored it -- relu(fma(v, a, b)) ROUNDED to T -- and only then compared, so y and idx are the bits of the two-kernel
+// path (the ReLU's exact zeros make ties the common case: the first tap in scan order must win them here too).  The normalised full-resolution tensor has no other
+// reader: its write and the pool's read of it are gone.  blockIdx.y = frame, so a workgroup needs one frame's group moments; thread = 8 channels of an output pixel.
+template <typename T>
+__global__ __launch_bounds__(256) void gn_relu_maxpool3s2_fwd_kernel(const T* __restrict__ x, const double* __restrict__ sums, const float* __restrict__ gamma,
+                                                                     const float* __restrict__ beta, T* __restrict__ y, uint8_t* __restrict__ idx, int H, int W,
+                                                                     int C, float eps, int Ho, int Wo, int top, int left) {
+    __shared__ float lmu[GN_G], lrs[GN_G];
+    const int n = blockIdx.y;
+    if (threadIdx.x < GN_G) gn_group_moments(sums, n, H * W, C, eps, lmu, lrs);
+    __syncthreads();
+    const int cb = C / 8;
+    const int i = (int)blockIdx.x * 256 + (int)threadIdx.x;               // within the frame
+    if (i >= Ho * Wo * cb) return;
+    const int c8 = (i % cb) * 8, pix = i / cb, wo = pix % Wo, ho = pix / Wo;
+    float a[8], b[8];
+    gn_affine8(gamma, beta, lmu, lrs, i % cb, C / GN_G, a, b);
+    float m[8]; int am[8];
+#pragma unroll
+    for (int j = 0; j < 8; ++j) { m[j] = -INFINITY; am[j] = 0; }
+    bool first = true;
+    for (int kh = 0; kh < 3; ++kh) {
+        const int h = 2 * ho - top + kh;
+        if (h < 0 || h >= H) continue;
+        for (int kw = 0; kw < 3; ++kw) {
+            const int w = 2 * wo - left + kw;
+            if (w < 0 || w >= W) continue;
+            float v[8];
+            ld8(x + (((int64_t)n * H + h) * W + w) * C + c8, v);
+#pragma unroll
+            for (int j = 0; j < 8; ++j) {
+                const float o = round_to<T>(fmaxf(fmaf(v[j], a[j], b[j]), 0.f));
+                if (first || o > m[j] || o != o) { m[j] = o; am[j] = kh * 3 + kw; }
+            }
+            first = false;
+        }
+    }
+    const int64_t e = (((int64_t)n * Ho * Wo) * cb + i) * 8;
+    st8(y + e, m);
+    uint32_t lo = 0, hi = 0;
+#pragma unroll
+    for (int j = 0; j < 4; ++j) { lo |= (uint32_t)am[j] << (8 * j); hi |= (uint32_t)am[4 + j] << (8 * j); }
+    *reinterpret_cast<uint2*>(idx + e) = make_uint2(lo, hi);
+}
+
 // Backward: a thread owns 8 channels of a 2 x 2 block of INPUT pixels chosen so that its four pixels lie under the same (at most four) windows -- rows
 // 2k - top, 2k - top + 1 see windows k - 1 and k -- and reads every window's gradient and winning taps ONCE for the four of them (round 6: one thread per input
 // pixel read them four times over: 99 us for 282 MB of compulsory traffic).  Per pixel the windows are added in the same order as before: the same bits.
@@ -878,6 +1018,24 @@ extern "C" int maed_maxpool3s2_same_fwd(const void* x, void* y, uint8_t* idx, in
     MAED_DISPATCH_DTYPE(dtype, T, hipLaunchKernelGGL((maxpool3s2_fwd_kernel<T>), dim3((unsigned)((n + 255) / 256)), dim3(256), 0, (hipStream_t)stream,
                                                       (const T*)x, (T*)y, idx, N, H, W, C, Ho, Wo, top, left));
     MAED_CHECK_LAUNCH("maxpool3s2_same_fwd");
+    return MAED_OK;
+}
+
+extern "C" int maed_gn_relu_maxpool3s2_fwd(const void* x, const float* gamma, const float* beta, void* y, uint8_t* idx, double* sums, int N, int H, int W, int C,
+                                           float eps, int dtype, int sums_zeroed, void* stream) {
+    MAED_CHECK_ARG(x && gamma && beta && y && idx && sums, MAED_ERR_ARG, "gn_relu_maxpool3s2_fwd: null pointer");
+    MAED_CHECK_ARG(H > 0 && W > 0 && (int64_t)H * W < ((int64_t)1 << 24), MAED_ERR_SHAPE, "gn_relu_maxpool3s2_fwd: H=%d W=%d (a frame's work items are counted in 32 bits)", H, W);
+    MAED_PROPAGATE(gn_check(C, H * W, "gn_relu_maxpool3s2_fwd"));
+    if (N <= 0) return MAED_OK;
+    MAED_CHECK_ARG(N <= 65535, MAED_ERR_SHAPE, "gn_relu_maxpool3s2_fwd: N=%d frames (one grid row per frame: at most 65535)", N);
+    hipStream_t s = (hipStream_t)stream;
+    MAED_PROPAGATE(gn_stats_if_needed(x, sums, N, H * W, C, dtype, sums_zeroed, s, "gn_relu_maxpool3s2_fwd"));
+    int Ho, Wo, top, left;
+    maxpool_geom(H, W, Ho, Wo, top, left);
+    const int per_frame = Ho * Wo * (C / 8);
+    MAED_DISPATCH_DTYPE(dtype, T, hipLaunchKernelGGL((gn_relu_maxpool3s2_fwd_kernel<T>), dim3((unsigned)((per_frame + 255) / 256), (unsigned)N), dim3(256), 0, s,
+                                                      (const T*)x, sums, gamma, beta, (T*)y, idx, H, W, C, eps, Ho, Wo, top, left));
+    MAED_CHECK_LAUNCH("gn_relu_maxpool3s2_fwd");
     return MAED_OK;
 }
 

@@ -1007,6 +1007,7 @@ class WeightStdFn(ReportingFn):
 # residual gradients handed on unmasked: data_ptr of the tensor -> (weakref to it, the ReLU bit mask that still has to be applied); consumed (popped) by
 # Conv1x1Fn.backward.  Keyed by address AND identity (the weakref must still point at the tensor that arrives).
 LAZY_RES = {}
+NORM_LATER = {}      # data pointer of a raw shortcut tensor's alias -> (weakref to it, gamma, beta, eps, sums, sums state, hand-over cell): GroupNormFn later=True
 
 
 GN_SYNC_WORDS = 80      # MAED_GN_SYNC_WORDS (include/maed_hip.h): 4-byte words per frame of maed_groupnorm_bwd's frame_sync scratch
@@ -1038,17 +1039,84 @@ def gn_affine_flush(device):
     pend.clear()
 
 
+def _groupnorm_backward(x, mask, dy, sums, gamma, beta, eps, relu, direct, ab, sync, want_dres):
+    """maed_groupnorm_bwd as the backbone's Functions call it: (dx, dres or None, dgamma, dbeta).  ab / sync: the layer's slices of the pass's zero-filled scratch
+    arena (single use; None: fresh scratch).  direct: dgamma / dbeta are gamma.grad / beta.grad, accumulated by the kernels (or by the pass's deferred column sum)."""
+    N, C_, H, W = x.shape
+    dx = torch.empty_like(x, memory_format=torch.channels_last)
+    dres = torch.empty_like(x, memory_format=torch.channels_last) if want_dres else None
+    if direct:
+        if gamma.grad is None:
+            gamma.grad = torch.zeros_like(gamma)
+        if beta.grad is None:
+            beta.grad = torch.zeros_like(beta)
+        dgamma, dbeta = gamma.grad, beta.grad
+    else:
+        dgamma = torch.zeros(C_, dtype=torch.float32, device=x.device)
+        dbeta = torch.zeros(C_, dtype=torch.float32, device=x.device)
+    ab_zeroed = ab is not None
+    if ab is None:
+        ab = torch.empty(N, C_, 2, dtype=torch.float32, device=x.device)
+    if sync is None:
+        sync = torch.zeros(N * GN_SYNC_WORDS, dtype=torch.int32, device=x.device)
+    # kernel-written dgamma / dbeta are read only after WeightStdFn.backward: with the pass's scratch arena (ab_zeroed) the closing column sum over the frames is
+    # DEFERRED -- the layer's partials stay in `ab` and ONE maed_gn_affine_grad_batch launch folds every layer of the pass (gn_affine_flush, called by
+    # WeightStdFn.backward and by the engine's end-of-pass callback): 52 launches of 6 us and 52 stream fences per step less (round 6).  Without the arena:
+    # the per-layer closing kernel on the side stream, as before.
+    defer = direct and ab_zeroed and GN_DEFER_AFFINE
+    aux = side_stream_handle(x.device, ab) if (direct and not defer) else None
+    check(L.lib().maed_groupnorm_bwd(_p(x), _p(mask), _p(dy), _p(sums), _p(gamma), _p(beta), _p(dx), _p(dres), None if defer else _p(dgamma),
+                                     None if defer else _p(dbeta), _p(ab), N, H * W, C_, eps, int(relu), dt_code(x.dtype), int(ab_zeroed), _p(sync), aux,
+                                     _stream()), "groupnorm_bwd")
+    if defer:
+        gn_affine_defer(x.device, ab, dgamma, dbeta, N, C_)
+    return dx, dres, dgamma, dbeta
+
+
 class GroupNormFn(torch.autograd.Function):
     """y = act(GroupNorm32(x) * gamma + beta [+ residual]) on channels_last tensors (maed_groupnorm_fwd/bwd).
     direct=True: gamma/beta gradients are accumulated by the kernel straight into gamma.grad / beta.grad (the
-    owner module reports them through its grads_ready callback) instead of travelling through autograd."""
+    owner module reports them through its grads_ready callback) instead of travelling through autograd.
+
+    A shortcut norm applied by its consumer (downsample blocks, bf16 without fp32 shadows): called with later=True, a norm without residual and activation launches
+    NOTHING -- it hands out an alias of its raw input and announces (gamma, beta, eps, sums) for it in NORM_LATER.  The block's closing norm finds its residual
+    there and runs maed_groupnorm_dual_fwd: both affines in one pass, the shortcut term rounded to the storage type as the stored tensor was -- the same bits
+    without the normalised shortcut tensor.  Backward: the closing norm writes the masked dy and the shortcut norm's backward reads it; or, when the closing norm
+    was called with lazy_res (as for identity blocks), it hands on dy itself with its ReLU bits and the shortcut norm's backward takes both: two
+    maed_groupnorm_bwd calls on the same dy and mask, no materialised shortcut gradient."""
 
     @staticmethod
-    def forward(ctx, x, residual, gamma, beta, eps, relu, direct, sums=None, ab=None, stats_ready=False, lazy_res=False, sync=None):
+    def forward(ctx, x, residual, gamma, beta, eps, relu, direct, sums=None, ab=None, stats_ready=False, lazy_res=False, sync=None, later=False):
         """sums (N,32,2) f64 / ab (N,C,2) f32: optional PRE-ZEROED scratch slices (ResNetV2 zeroes one arena per pass for all
         its 52 layers instead of one memset per layer and direction).  stats_ready: `sums` already holds the statistics of x (the
         producing convolution's epilogue accumulated them: Conv1x1Fn / Conv3x3Fn gn_sums) -- no statistics pass."""
         N, C_, H, W = x.shape
+        ctx.later = bool(later)
+        if later:
+            assert residual is None and not relu and shadow_of(x) is None, "GroupNormFn later=True: a plain norm of an unshadowed tensor"
+            x = x.contiguous(memory_format=torch.channels_last)
+            zeroed = sums is not None
+            if sums is None:
+                sums = torch.empty(N, 32, 2, dtype=torch.float64, device=x.device)
+            xa = x.view_as(x)
+            for k in [k for k, ent in NORM_LATER.items() if ent[0]() is None]:      # announcements whose consumer never ran
+                del NORM_LATER[k]
+            # handover[0]: set by the consumer's forward -- True: its backward hands on its own dy with the ReLU bits (LAZY_RES), False: a materialised masked dy
+            ctx.handover = [None]
+            NORM_LATER[xa.data_ptr()] = (weakref.ref(xa), gamma, beta, eps, sums, 2 if (stats_ready and zeroed) else int(zeroed), ctx.handover)
+            ctx.ab = ab
+            ctx.sync = sync if ab is not None else None
+            ctx.save_for_backward(x, None, sums)
+            ctx.eps, ctx.relu, ctx.direct, ctx.has_res, ctx.lazy_res = eps, False, direct, False, False
+            ctx.gamma, ctx.beta = gamma, beta
+            return xa
+        fold = NORM_LATER.pop(residual.data_ptr(), None) if residual is not None else None
+        if fold is not None and fold[0]() is None:      # a stale announcement at a recycled address
+            fold = None
+        if fold is not None and fold[0]() is not residual:
+            raise RuntimeError("GroupNormFn: a norm was announced for this residual (later=True) but another tensor arrived -- its alias must feed the closing norm directly")
+        if fold is not None:
+            assert relu and shadow_of(x) is None and residual.dtype == x.dtype and residual.shape == x.shape, "GroupNormFn: a folded shortcut norm needs relu, one dtype, no shadows"
         x32 = shadow_of(x)                       # bf16 graph over fp32 shadows (shadow_put): the forward runs on the shadows, the twins are what is saved
         r32 = shadow_of(residual) if x32 is not None else None
         if x32 is not None and not x.is_contiguous(memory_format=torch.channels_last):
@@ -1076,6 +1144,10 @@ class GroupNormFn(torch.autograd.Function):
                                                   2 if (stats_ready and zeroed) else int(zeroed), _p(x) if fill_x else None, _p(y16), _stream()), "groupnorm_fwd_twin")
             _UNFILLED.discard(x.data_ptr())
             y = shadow_put(y16, y)
+        elif fold is not None:
+            _, gamma2, beta2, eps2, sums2, stats2, handover = fold
+            check(L.lib().maed_groupnorm_dual_fwd(_p(xin), _p(gamma), _p(beta), _p(sums), _p(rin), _p(gamma2), _p(beta2), _p(sums2), _p(y), _p(mask), N, H * W, C_, eps,
+                                                  eps2, dt_code(xin.dtype), 2 if (stats_ready and zeroed) else int(zeroed), stats2, _stream()), "groupnorm_dual_fwd")
         else:
             check(L.lib().maed_groupnorm_fwd(_p(xin), _p(rin), _p(gamma), _p(beta), _p(y), _p(sums), _p(mask), N, H * W, C_, eps, int(relu),
                                              dt_code(xin.dtype), 2 if (stats_ready and zeroed) else int(zeroed), _stream()), "groupnorm_fwd")
@@ -1086,6 +1158,8 @@ class GroupNormFn(torch.autograd.Function):
         # lazy_res: the residual's gradient (dy masked by the ReLU bits) is not materialised -- backward hands dy itself on and registers the bit mask
         # for it; the consumer (Conv1x1Fn.backward of the block's conv1, which adds the shortcut gradient inside its input-gradient GEMM) applies it
         ctx.lazy_res = bool(lazy_res) and need_mask
+        if fold is not None:
+            fold[6][0] = ctx.lazy_res
         ctx.gamma, ctx.beta = gamma, beta   # parameters (leaf tensors): kept by reference for .grad access
         return y
 
@@ -1093,44 +1167,28 @@ class GroupNormFn(torch.autograd.Function):
     def backward(ctx, dy):
         x, mask, sums = ctx.saved_tensors
         gamma, beta = ctx.gamma, ctx.beta
-        N, C_, H, W = x.shape
+        relu = ctx.relu
+        if ctx.later:
+            # the closing norm either materialised the masked dy (a plain norm backward on it) or handed on its own dy with the ReLU bits (lazy_res): then this is
+            # the same call as its own with this norm's tensors -- relu = 1 with the forward's mask: the YMASK kernels, which never recompute a ReLU from gamma / beta
+            if ctx.handover[0]:
+                ent = LAZY_RES.pop(dy.data_ptr(), None)
+                if ent is None or ent[0]() is not dy:
+                    raise RuntimeError("GroupNormFn later=True: the closing norm announced its own dy with the ReLU bits (lazy_res) but another tensor arrived -- "
+                                       "the alias must feed exactly one closing norm")
+                mask, relu = ent[1], True
         dy = dy.contiguous(memory_format=torch.channels_last)
-        dx = torch.empty_like(x, memory_format=torch.channels_last)
-        dres = torch.empty_like(x, memory_format=torch.channels_last) if (ctx.has_res and not ctx.lazy_res) else None
-        if ctx.direct:
-            if gamma.grad is None:
-                gamma.grad = torch.zeros_like(gamma)
-            if beta.grad is None:
-                beta.grad = torch.zeros_like(beta)
-            dgamma, dbeta = gamma.grad, beta.grad
-        else:
-            dgamma = torch.zeros(C_, dtype=torch.float32, device=x.device)
-            dbeta = torch.zeros(C_, dtype=torch.float32, device=x.device)
-        ab, ab_zeroed, sync = ctx.ab, ctx.ab is not None, ctx.sync
+        ab, sync = ctx.ab, ctx.sync
         ctx.ab = ctx.sync = None                        # single use: a second backward through this node gets fresh scratch
-        if ab is None:
-            ab = torch.empty(N, C_, 2, dtype=torch.float32, device=x.device)
-        if sync is None:
-            sync = torch.zeros(N * GN_SYNC_WORDS, dtype=torch.int32, device=x.device)
-        # kernel-written dgamma / dbeta are read only after WeightStdFn.backward: with the pass's scratch arena (ab_zeroed) the closing column sum over the frames is
-        # DEFERRED -- the layer's partials stay in `ab` and ONE maed_gn_affine_grad_batch launch folds every layer of the pass (gn_affine_flush, called by
-        # WeightStdFn.backward and by the engine's end-of-pass callback): 52 launches of 6 us and 52 stream fences per step less (round 6).  Without the arena:
-        # the per-layer closing kernel on the side stream, as before.
-        defer = ctx.direct and ab_zeroed and GN_DEFER_AFFINE
-        aux = side_stream_handle(x.device, ab) if (ctx.direct and not defer) else None
-        check(L.lib().maed_groupnorm_bwd(_p(x), _p(mask), _p(dy), _p(sums), _p(gamma), _p(beta), _p(dx), _p(dres), None if defer else _p(dgamma),
-                                         None if defer else _p(dbeta), _p(ab), N, H * W, C_, ctx.eps, int(ctx.relu), dt_code(x.dtype), int(ab_zeroed), _p(sync), aux,
-                                         _stream()), "groupnorm_bwd")
-        if defer:
-            gn_affine_defer(x.device, ab, dgamma, dbeta, N, C_)
+        dx, dres, dgamma, dbeta = _groupnorm_backward(x, mask, dy, sums, gamma, beta, ctx.eps, relu, ctx.direct, ab, sync, ctx.has_res and not ctx.lazy_res)
         if ctx.lazy_res:
             for k in [k for k, (r, _) in LAZY_RES.items() if r() is None]:      # announcements whose consumer never ran (an interrupted backward)
                 del LAZY_RES[k]
             LAZY_RES[dy.data_ptr()] = (weakref.ref(dy), mask)
             dres = dy
         if ctx.direct:
-            return dx, dres, None, None, None, None, None, None, None, None, None, None
-        return dx, dres, dgamma, dbeta, None, None, None, None, None, None, None, None
+            return dx, dres, None, None, None, None, None, None, None, None, None, None, None
+        return dx, dres, dgamma, dbeta, None, None, None, None, None, None, None, None, None
 
 
 def stem_input(x, dtype, k, s, own=False):
@@ -1218,6 +1276,46 @@ class MaxPool3s2SameFn(torch.autograd.Function):
         dx = torch.empty((N, C_, H, W), dtype=dy.dtype, device=dy.device, memory_format=torch.channels_last)
         check(L.lib().maed_maxpool3s2_same_bwd(_p(dy), _p(idx), _p(dx), N, H, W, C_, dt_code(dy.dtype), _stream()), "maxpool3s2_same_bwd")
         return dx
+
+
+class GroupNormReluMaxPoolFn(torch.autograd.Function):
+    """The stem's GroupNormAct + MaxPool2dSame(3, 2) in one forward pass (maed_gn_relu_maxpool3s2_fwd): x is the raw stem convolution output, the normalised
+    full-resolution tensor is never written (bit for bit GroupNormFn(relu) -> MaxPool3s2SameFn).  Backward as those two: the pool's gather backward, then
+    maed_groupnorm_bwd on the saved x.  Compute-dtype tensors without fp32 shadows only (the caller gates); sums / ab / sync / stats_ready / direct as GroupNormFn."""
+
+    @staticmethod
+    def forward(ctx, x, gamma, beta, eps, direct, sums=None, ab=None, stats_ready=False, sync=None):
+        N, C_, H, W = x.shape
+        assert shadow_of(x) is None, "GroupNormReluMaxPoolFn: shadowed input (the fp32-forward modes keep the two-kernel path)"
+        x = x.contiguous(memory_format=torch.channels_last)
+        Ho, Wo = (H + 1) // 2, (W + 1) // 2
+        y = torch.empty((N, C_, Ho, Wo), dtype=x.dtype, device=x.device, memory_format=torch.channels_last)
+        idx = torch.empty(N * Ho * Wo * C_, dtype=torch.uint8, device=x.device)
+        zeroed = sums is not None
+        if sums is None:
+            sums = torch.empty(N, 32, 2, dtype=torch.float64, device=x.device)
+        check(L.lib().maed_gn_relu_maxpool3s2_fwd(_p(x), _p(gamma), _p(beta), _p(y), _p(idx), _p(sums), N, H, W, C_, eps, dt_code(x.dtype),
+                                                  2 if (stats_ready and zeroed) else int(zeroed), _stream()), "gn_relu_maxpool3s2_fwd")
+        ctx.ab = ab
+        ctx.sync = sync if ab is not None else None
+        ctx.save_for_backward(x, sums, idx)
+        ctx.eps, ctx.direct = eps, direct
+        ctx.gamma, ctx.beta = gamma, beta
+        return y
+
+    @staticmethod
+    def backward(ctx, dy):
+        x, sums, idx = ctx.saved_tensors
+        N, C_, H, W = x.shape
+        dy = dy.contiguous(memory_format=torch.channels_last)
+        dpool = torch.empty((N, C_, H, W), dtype=dy.dtype, device=dy.device, memory_format=torch.channels_last)
+        check(L.lib().maed_maxpool3s2_same_bwd(_p(dy), _p(idx), _p(dpool), N, H, W, C_, dt_code(dy.dtype), _stream()), "maxpool3s2_same_bwd")
+        ab, sync = ctx.ab, ctx.sync
+        ctx.ab = ctx.sync = None
+        dx, _, dgamma, dbeta = _groupnorm_backward(x, None, dpool, sums, ctx.gamma, ctx.beta, ctx.eps, True, ctx.direct, ab, sync, False)
+        if ctx.direct:
+            return dx, None, None, None, None, None, None, None, None
+        return dx, dgamma, dbeta, None, None, None, None, None, None
 
 
 class Conv1x1Fn(torch.autograd.Function):

@@ -45,6 +45,19 @@ _LAZY_RES_GRAD = os.environ.get("MAED_GN_LAZY_DRES", "1") == "1"
 # a separate pass over the activation (52 launches, 0.64 ms per step at cfg3).  MAED_GN_FUSE_STATS=0 switches back (A/B knob).
 _FUSE_GN_STATS = os.environ.get("MAED_GN_FUSE_STATS", "1") == "1"
 
+# bf16 library path: the stem's GroupNorm + ReLU applied inside the max-pool's forward pass (ops.GroupNormReluMaxPoolFn) -- the normalised 112 x 112 tensor is never
+# written.  MAED_STEM_FUSE_POOL=0: norm and pool as two kernels (A/B knob).
+_FUSE_STEM_POOL = os.environ.get("MAED_STEM_FUSE_POOL", "1") == "1"
+
+# bf16 library path, blocks with a downsample shortcut: the shortcut's GroupNorm applied inside the block's closing GroupNorm + add + ReLU pass
+# (ops.GroupNormFn later=True) -- the normalised shortcut is never written.  MAED_GN_FUSE_SHORTCUT=0: DownsampleConv's own norm pass (A/B knob).
+_FUSE_SHORTCUT_NORM = os.environ.get("MAED_GN_FUSE_SHORTCUT", "1") == "1"
+# ... MAED_GN_FUSE_SHORTCUT_DRES=1: the backward of the fused form hands both norms dy and the ReLU bits instead of materialising the shortcut's gradient (as the
+# identity blocks' MAED_GN_LAZY_DRES).  Default OFF: the closing norm's backward writes dres, the shortcut norm's backward reads it.  The kernel trace gives the
+# lazy form 21 us per step (the three closing backwards lose a write, the three shortcut backwards gain the mask read), the step shows nothing: three interleaved
+# rounds 19.010 / 19.115 / 19.110 ms with it, 19.085 / 19.111 / 19.111 without (profiles/gnfold_bench_ab.txt) -- not claimed, kept as an A/B knob.
+_LAZY_SHORTCUT_DRES = os.environ.get("MAED_GN_FUSE_SHORTCUT_DRES", "0") == "1"
+
 
 def _ws_per_stage():
     if _WS_PER_STAGE is not None:
@@ -181,17 +194,35 @@ class GroupNormAct(nn.GroupNorm):
         super().__init__(num_groups, num_channels, eps=eps, affine=affine)
         self.apply_act = apply_act
 
-    def forward(self, x, residual=None, relu=None, lazy_res=False):
-        """y = act(GN(x) [+ residual]); relu defaults to the layer's own activation flag"""
+    def forward(self, x, residual=None, relu=None, lazy_res=False, later=False):
+        """y = act(GN(x) [+ residual]); relu defaults to the layer's own activation flag.
+        later=True (a shortcut's norm, see fuses_with): an alias of x comes back -- the norm is applied by the closing norm that takes it as its residual.
+        (A forward hook on such a norm therefore sees the RAW tensor, and with the stem fold stem.norm / stem.pool are not called at all: per-module
+        diagnostics switch the folds off, as scripts/diag_backbone_bf16.py does.)"""
         relu = self.apply_act if relu is None else relu
         if ops.on_library_device(x) and self.num_groups == 32:
-            ready, self._stats_ready = self._stats_ready and self._sums_buf is not None, False
+            ready = self._take_stats_ready()
             return ops.GroupNormFn.apply(x, residual, self.weight, self.bias, self.eps, relu, self._direct_grad, self._sums_buf, self._ab_buf, ready, lazy_res,
-                                         self._sync_buf)
+                                         self._sync_buf, later)
+        assert not later
         x = F.group_norm(x, self.num_groups, self.weight.to(x.dtype), self.bias.to(x.dtype), self.eps)
         if residual is not None:
             x = x + residual
         return F.relu(x) if relu else x
+
+    def _take_stats_ready(self):
+        ready, self._stats_ready = self._stats_ready and self._sums_buf is not None, False
+        return ready
+
+    def fuses_with(self, x, other=None):
+        """the one-pass forms (forward_pool; `other`: the shortcut's norm applied by this closing norm) take bf16 library tensors without fp32 shadows, 32 groups"""
+        return (ops.on_library_device(x) and x.dtype == torch.bfloat16 and ops.shadow_of(x) is None and self.num_groups == 32
+                and (other is None or (other.num_groups == 32 and not other.apply_act and other.num_channels == self.num_channels)))
+
+    def forward_pool(self, x):
+        """MaxPool2dSame(3, 2)(relu(GN(x))) in one pass over the raw convolution output x (the stem)"""
+        return ops.GroupNormReluMaxPoolFn.apply(x, self.weight, self.bias, self.eps, self._direct_grad, self._sums_buf, self._ab_buf, self._take_stats_ready(),
+                                                self._sync_buf)
 
 
 class MaxPool2dSame(nn.Module):
@@ -243,15 +274,27 @@ class Bottleneck(nn.Module):
             # conv1's input-gradient GEMM applies the bits while it adds (ops.GroupNormFn lazy_res / Conv1x1Fn lazy_short)
             lazy = self.downsample is None and _LAZY_RES_GRAD
             y, xa = self.conv1(x, fork=True, gn=self.norm1, lazy_short=lazy)
-            shortcut = xa if self.downsample is None else self.downsample(xa)
+            shortcut, folded = (xa, False) if self.downsample is None else self._shortcut(xa)
             x = self.norm1(y)
             x = self.norm2(self.conv2(x, gn=self.norm2))
-            return self.norm3(self.conv3(x, gn=self.norm3), residual=shortcut, relu=True, lazy_res=lazy)
+            return self._close(self.conv3(x, gn=self.norm3), shortcut, folded, lazy)
         else:
-            shortcut = x if self.downsample is None else self.downsample(x)
+            shortcut, folded = (x, False) if self.downsample is None else self._shortcut(x)
             x = self.norm1(self.conv1(x, gn=self.norm1))
         x = self.norm2(self.conv2(x, gn=self.norm2))      # (gn=: the convolution's epilogue accumulates the GroupNorm statistics)
-        return self.norm3(self.conv3(x, gn=self.norm3), residual=shortcut, relu=True)   # GN + shortcut add + ReLU in one pass
+        return self._close(self.conv3(x, gn=self.norm3), shortcut, folded, False)
+
+    def _shortcut(self, x):
+        """(shortcut, its norm still to be applied?): with _FUSE_SHORTCUT_NORM the downsample convolution's raw output comes back (as the alias its norm hands
+        out, ops.GroupNormFn later=True) and the block's closing pass applies that norm"""
+        ds = self.downsample
+        if _FUSE_SHORTCUT_NORM and self.norm3.fuses_with(x, ds.norm):
+            return ds.norm(ds.conv(x, gn=ds.norm), later=True), True
+        return ds(x), False
+
+    def _close(self, y, shortcut, folded, lazy):
+        """norm3 + shortcut add + ReLU in one pass; folded: + the shortcut's own norm (with _LAZY_SHORTCUT_DRES its gradient is handed on unmasked with the ReLU bits)"""
+        return self.norm3(y, residual=shortcut, relu=True, lazy_res=(folded and _LAZY_SHORTCUT_DRES) or lazy)
 
 
 class ResNetStage(nn.Module):
@@ -416,18 +459,27 @@ class ResNetV2(nn.Module):
                 _slots(m, _ab_buf=ab[off:off + n].view(N, m.num_channels, 2), _sync_buf=ab[off + n:off + n + N * ops.GN_SYNC_WORDS])
                 off += n + N * ops.GN_SYNC_WORDS
         if ws is not None:
-            return self.stages(self.stem(x))
+            return self.stages(self._stem_library(x))
         for gi, g in enumerate(self._ws_groups):       # standardise a stage's weights right before it runs: its autograd node
             wg = self._standardise(g, cdt, twin)                                                       # then fires right after its backward
             for k, (ci, w) in enumerate(zip(g.conv_idx, wg)):
                 c = self._convs[ci]
                 _slots(c, _w_std=w, _w_t=g._w_std_t.get(k), _dw=g._dw_slices.get(k), _prec=self.f32_matmul)
-            x = self.stages[0](self.stem(x)) if gi == 0 else self.stages[gi](x)
+            x = self.stages[0](self._stem_library(x)) if gi == 0 else self.stages[gi](x)
         # backward order is last stage first: every group but the one that runs last may finish on the side stream (ops.WeightStdFn.backward)
         runs = [g for g in self._ws_groups if g._pending_backwards > 0]
         for k, g in enumerate(self._ws_groups):
             g._ws_on_side = bool(runs) and g is not runs[0] and g in runs
         return x
+
+    def _stem_library(self, x):
+        """the stem on the library device: convolution, then norm + ReLU + pool -- in one pass over the raw convolution output where that form applies"""
+        stem = self.stem
+        y = stem.conv(x)
+        if (_FUSE_STEM_POOL and stem.norm.apply_act and stem.norm.fuses_with(y) and (stem.pool.kernel_size, stem.pool.stride) == (3, 2)
+                and y.shape[2] * y.shape[3] < 1 << 24):
+            return stem.norm.forward_pool(y)
+        return stem.pool(stem.norm(y))
 
     def _standardise(self, owner, cdt, twin):
         """the batched weight standardisation of `owner` (the backbone or one stage group) in the pass's dtype; twin: + the fp32 images of the same weights for the

@@ -2,6 +2,10 @@
 usage: diag_backbone_bf16.py [n_frames=4] [img=224]"""
 import os, sys
 import torch
+# per-module hooks compare what each module RETURNS: with the norms folded into their consumers (maed_amd/resnetv2.py) stem.norm / stem.pool are not called and
+# downsample.norm returns the raw convolution output -- this diagnostic runs the unfolded path (same bits)
+os.environ["MAED_STEM_FUSE_POOL"] = "0"
+os.environ["MAED_GN_FUSE_SHORTCUT"] = "0"
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 from maed_amd.resnetv2 import ResNetV2
 from oracle import maed_ref as R
