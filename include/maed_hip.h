@@ -20,7 +20,8 @@
  *  - row-major everywhere; "ld" arguments are leading dimensions in ELEMENTS.
  *  - token layout: tokens[(f*P + p)*C + c], f = n*T + t (frames of a clip are contiguous),
  *    qkv[(f*P + p)*3C + s*C + h*64 + e]   (vision_transformer.py:147 channel order s, h, e).
- *  - head dimension is 64 in every supported configuration (C = 64*H).
+ *  - head dimension D = C / H: 64 is the tuned size (every kernel family); 32, 96 and 128 run on the head-size-generic tiled kernels
+ *    (maed_attn_seq_fwd / _bwd, and the fused block with C = D*H).  qkv[(f*P + p)*3C + s*C + h*D + e] then.
  */
 #ifndef MAED_HIP_H
 #define MAED_HIP_H
@@ -215,6 +216,20 @@ int maed_attn_temporal_bwd(const void* qkv, const void* o, const void* d_o, cons
                            void* dqkv, int accumulate, int F, int P, int H, int T, float scale,
                            int dtype, void* stream);
 
+/* ---- K3 / K4 for head sizes D in {32, 64, 96, 128} (vision_transformer.py:160-163,206-228) ------ */
+/* The same attention over strided sequences: `groups` groups of `len` x `inner` token rows; sequence (g, h, i) is rows g*len*inner + j*inner + i (j < len) of
+ * qkv (rows, 3C), channels h*D .. h*D + D - 1 of the q | k | v blocks, C = D*H.
+ *   spatial attention : groups = F,   len = P,   inner = 1      coupling : groups = F/T, len = T*P, inner = 1
+ *   temporal attention: groups = F/T, len = T,   inner = P      (reads and writes the (F,P,3C) / (F,P,C) layouts in place)
+ * o (rows, C); lse fp32, natural log: inner == 1: (groups, H, len); inner > 1: (groups*len, H, inner) -- the layouts of the entry points above.
+ * dtype MAED_BF16: K/V-tiled MFMA kernels (impl MAED_IMPL_AUTO / MAED_IMPL_MFMA_LONG) or the exact kernels in bf16 storage (MAED_IMPL_VALU);
+ * dtype MAED_F32: the exact fp32 kernels, whatever MAED_OPT_F32_MATMUL says.  Selectors of kernels that exist for D = 64 only (MAED_IMPL_MFMA,
+ * MAED_IMPL_X3 / _X6) and other head sizes: MAED_ERR_UNSUPPORTED.  maed_attn_spatial_* / maed_attn_temporal_* keep meaning D = 64 and never come here. */
+int maed_attn_seq_fwd(const void* qkv, void* o, float* lse, int groups, int len, int inner, int H, int head_dim,
+                      float scale, int dtype, int impl, void* stream);
+int maed_attn_seq_bwd(const void* qkv, const void* o, const void* d_o, const float* lse, void* dqkv, int accumulate,
+                      int groups, int len, int inner, int H, int head_dim, float scale, int dtype, int impl, void* stream);
+
 /* ---- K5: attentive addition (vision_transformer.py:152-158) ----------------------------------- */
 /* means[T](F,2C) = mean over tokens of [x_s || x_t];  ws: caller-owned fp32 scratch of F*2C floats */
 int maed_st_colmean(const void* x_s, const void* x_t, void* means, float* ws, int F, int P, int C, int dtype, void* stream);
@@ -265,9 +280,9 @@ int maed_tanh_bwd(const float* dy, const void* y, void* dx, int64_t n, int dtype
 /* ---- whole STE Block (vision_transformer.py:244-261 with Attention 'parallel' :146-158,176 and
  *      Mlp :106-112) as ONE host call that enqueues every kernel of the block -------------------- */
 typedef struct {
-    int F, P, C, H, T, hidden; /* frames, tokens/frame, embed dim, heads, clip length, MLP hidden */
+    int F, P, C, H, T, hidden; /* frames, tokens/frame, embed dim, heads (C / H in {32, 64, 96, 128}), clip length, MLP hidden */
     int dtype;                 /* maed_dtype of activations + GEMM weights */
-    int impl;                  /* maed_impl for attention / GEMM */
+    int impl;                  /* maed_impl for attention / GEMM; C / H != 64: MAED_IMPL_AUTO or MAED_IMPL_VALU (else MAED_ERR_UNSUPPORTED) */
     float eps;                 /* LayerNorm eps (1e-6) */
 } maed_block_dims;
 

@@ -61,6 +61,7 @@ class LossWeights(C.Structure):
 
 
 KTD_W_ANC = 3420
+HEAD_DIMS = (32, 64, 96, 128)     # C / H the attention kernels cover: 64 on every kernel family, the others on maed_attn_seq_*
 
 # name -> (restype, argtypes): mirrors include/maed_hip.h one to one (tests/test_cabi.py checks it)
 SIGNATURES = {
@@ -80,6 +81,8 @@ SIGNATURES = {
     "maed_attn_spatial_bwd": (i32, [vp, vp, vp, vp, vp, i32, i32, i32, i32, f32, i32, i32, vp]),
     "maed_attn_temporal_fwd": (i32, [vp, vp, vp, i32, i32, i32, i32, f32, i32, vp]),
     "maed_attn_temporal_bwd": (i32, [vp, vp, vp, vp, vp, i32, i32, i32, i32, i32, f32, i32, vp]),
+    "maed_attn_seq_fwd": (i32, [vp, vp, vp, i32, i32, i32, i32, i32, f32, i32, i32, vp]),
+    "maed_attn_seq_bwd": (i32, [vp, vp, vp, vp, vp, i32, i32, i32, i32, i32, i32, f32, i32, i32, vp]),
     "maed_st_colmean": (i32, [vp, vp, vp, vp, i32, i32, i32, i32, vp]),
     "maed_st_mix_fwd": (i32, [vp, vp, vp, vp, i32, i32, i32, i32, vp]),
     "maed_st_mix_bwd_reduce": (i32, [vp, vp, vp, vp, vp, vp, i32, i32, i32, i32, vp]),

@@ -586,3 +586,6 @@ int maed_attn_long_bwd_valu_launch(const void* qkv, const void* o, const void* d
     MAED_CHECK_LAUNCH("attn_long_bwd(valu)");
     return MAED_OK;
 }
+
+// head sizes 32 / 96 / 128 (and the strided sequences of temporal attention): the same kernels as templates on the head size, maed_attn_seq_{fwd,bwd}
+#include "attn_heads.hip"

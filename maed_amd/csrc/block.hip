@@ -218,10 +218,34 @@ int check_dims(const maed_block_dims* d, const char* who) {
     MAED_CHECK_ARG(d, MAED_ERR_ARG, "%s: null dims", who);
     MAED_CHECK_ARG(d->dtype == MAED_F32 || d->dtype == MAED_BF16, MAED_ERR_ARG, "%s: bad dtype %d", who, d->dtype);
     MAED_CHECK_ARG(d->F > 0 && d->P > 0 && d->H > 0 && d->T > 0 && d->hidden > 0, MAED_ERR_SHAPE, "%s: non-positive extent", who);
-    MAED_CHECK_ARG(d->C == d->H * HEAD_DIM, MAED_ERR_SHAPE, "%s: C=%d must equal 64*H (H=%d)", who, d->C, d->H);
+    const int hd = d->C / d->H;
+    MAED_CHECK_ARG(d->C == d->H * hd && (hd == 32 || hd == 64 || hd == 96 || hd == 128), MAED_ERR_SHAPE, "%s: C=%d must equal D*H with D in {32, 64, 96, 128} (H=%d)", who,
+                   d->C, d->H);
+    MAED_CHECK_ARG(hd == HEAD_DIM || d->impl == MAED_IMPL_AUTO || d->impl == MAED_IMPL_VALU, MAED_ERR_UNSUPPORTED,
+                   "%s: impl %d names an attention kernel that exists for head size 64 only (C/H = %d takes MAED_IMPL_AUTO or MAED_IMPL_VALU)", who, d->impl, hd);
     MAED_CHECK_ARG(d->F % d->T == 0, MAED_ERR_SHAPE, "%s: F=%d not a multiple of T=%d", who, d->F, d->T);
     MAED_CHECK_ARG(d->hidden % 64 == 0, MAED_ERR_SHAPE, "%s: hidden=%d must be a multiple of 64", who, d->hidden);
     return MAED_OK;
+}
+
+// the block's two attentions.  C / H = 64: the entry points (and dispatch) the block has always used, argument for argument; other head sizes: the head-size-generic
+// tiled kernels of csrc/attn_heads.hip on the same buffers (fp32 there means the exact kernels, whatever the process-wide fp32 matmul mode is)
+int attn_tm_fwd(const maed_block_dims* d, const void* qkv, void* o, float* lse, float scale, void* st) {
+    if (d->C == d->H * HEAD_DIM) return maed_attn_temporal_fwd(qkv, o, lse, d->F, d->P, d->H, d->T, scale, d->dtype, st);
+    return maed_attn_seq_fwd(qkv, o, lse, d->F / d->T, d->T, d->P, d->H, d->C / d->H, scale, d->dtype, d->impl == MAED_IMPL_VALU ? MAED_IMPL_VALU : MAED_IMPL_AUTO, st);
+}
+int attn_sp_fwd(const maed_block_dims* d, const void* qkv, void* o, float* lse, float scale, void* st) {
+    if (d->C == d->H * HEAD_DIM) return maed_attn_spatial_fwd(qkv, o, lse, d->F, d->P, d->H, scale, d->dtype, d->impl, st);
+    return maed_attn_seq_fwd(qkv, o, lse, d->F, d->P, 1, d->H, d->C / d->H, scale, d->dtype, d->impl == MAED_IMPL_VALU ? MAED_IMPL_VALU : MAED_IMPL_AUTO, st);
+}
+int attn_tm_bwd(const maed_block_dims* d, const void* qkv, const void* o, const void* d_o, const float* lse, void* dqkv, int accumulate, float scale, void* st) {
+    if (d->C == d->H * HEAD_DIM) return maed_attn_temporal_bwd(qkv, o, d_o, lse, dqkv, accumulate, d->F, d->P, d->H, d->T, scale, d->dtype, st);
+    return maed_attn_seq_bwd(qkv, o, d_o, lse, dqkv, accumulate, d->F / d->T, d->T, d->P, d->H, d->C / d->H, scale, d->dtype,
+                             d->impl == MAED_IMPL_VALU ? MAED_IMPL_VALU : MAED_IMPL_AUTO, st);
+}
+int attn_sp_bwd(const maed_block_dims* d, const void* qkv, const void* o, const void* d_o, const float* lse, void* dqkv, int accumulate, float scale, int impl, void* st) {
+    if (d->C == d->H * HEAD_DIM) return maed_attn_spatial_bwd(qkv, o, d_o, lse, dqkv, accumulate, d->F, d->P, d->H, scale, d->dtype, impl, st);
+    return maed_attn_seq_bwd(qkv, o, d_o, lse, dqkv, accumulate, d->F, d->P, 1, d->H, d->C / d->H, scale, d->dtype, impl, st);
 }
 
 // the attentive addition as one launch per direction (bf16 MFMA mode; MAED_OPT_ST_FUSED = 0 keeps the four-launch sequence: A/B knob)
@@ -280,7 +304,7 @@ static int block_fwd_bufs(const maed_block_dims* d, const maed_block_params* p, 
     const int64_t M = (int64_t)d->F * d->P;
     const int C = d->C, Hd = d->hidden, dt = d->dtype;
     const int gi = d->impl == MAED_IMPL_VALU ? MAED_IMPL_VALU : MAED_IMPL_AUTO;
-    const float scale = 1.0f / sqrtf((float)HEAD_DIM);
+    const float scale = 1.0f / sqrtf((float)(d->C / d->H));
     float* logits = (float*)B.logits;
 
     // (the LayerNorm kernel also zeroes the per-frame arrival counters of the fused attentive addition further down: no memset launch of their own)
@@ -308,8 +332,8 @@ static int block_fwd_bufs(const maed_block_dims* d, const maed_block_params* p, 
         SideStream* ss = (d->impl != MAED_IMPL_VALU && (dt == MAED_BF16 || maed_x3_planes())) ? side_stream() : nullptr;
         void* tst = ss ? (void*)ss->s : stream;
         if (ss) ss->fence((hipStream_t)stream, ss->s);
-        { ProfScope ps__(PROF_ATTN_TM_FWD, tst); MAED_PROPAGATE(maed_attn_temporal_fwd(B.qkv, B.xt, (float*)(B.lse_t), d->F, d->P, d->H, d->T, scale, dt, tst)); }
-        PROF(PROF_ATTN_SP_FWD, maed_attn_spatial_fwd(B.qkv, B.xs, (float*)(B.lse_s), d->F, d->P, d->H, scale, dt, d->impl, stream));
+        { ProfScope ps__(PROF_ATTN_TM_FWD, tst); MAED_PROPAGATE(attn_tm_fwd(d, B.qkv, B.xt, (float*)(B.lse_t), scale, tst)); }
+        PROF(PROF_ATTN_SP_FWD, attn_sp_fwd(d, B.qkv, B.xs, (float*)(B.lse_s), scale, stream));
         if (ss) ss->fence(ss->s, (hipStream_t)stream);
     }
     if (stf) {       // token means + ts_attn Linear + pair softmax + mix: one launch, x_s / x_t read once (elementwise.hip)
@@ -386,6 +410,7 @@ extern "C" size_t maed_ste_block_twin_work_bytes(const maed_block_dims* d) {
 extern "C" int maed_ste_block_fwd_twin(const maed_block_dims* d, const maed_block_params* p, const float* x_in, float* x_out, void* saved_bf16, void* work_f32,
                                        int work_slot, void* stream) {
     MAED_PROPAGATE(check_dims(d, "ste_block_fwd_twin"));
+    MAED_CHECK_ARG(d->C == d->H * HEAD_DIM, MAED_ERR_UNSUPPORTED, "ste_block_fwd_twin: head size %d (the twin forward exists for head size 64 only)", d->C / d->H);
     MAED_CHECK_ARG(d->dtype == MAED_F32, MAED_ERR_ARG, "ste_block_fwd_twin: dims describe the FORWARD (dtype MAED_F32); the arena is laid out for MAED_BF16");
     MAED_CHECK_ARG(p && x_in && x_out && saved_bf16 && work_f32, MAED_ERR_ARG, "ste_block_fwd_twin: null pointer");
     MAED_CHECK_ARG(is_aligned(saved_bf16, 256) && is_aligned(work_f32, 256), MAED_ERR_ALIGN, "ste_block_fwd_twin: buffers must be 256-B aligned");
@@ -457,11 +482,11 @@ extern "C" int maed_ste_block_bwd(const maed_block_dims* d, const maed_block_par
     const int64_t M = (int64_t)d->F * d->P, Mp = S.Mp, Fp = S.Fp;
     const int C = d->C, Hd = d->hidden, dt = d->dtype;
     const int gi = d->impl == MAED_IMPL_VALU ? MAED_IMPL_VALU : MAED_IMPL_AUTO;
-    const float scale = 1.0f / sqrtf((float)HEAD_DIM);
+    const float scale = 1.0f / sqrtf((float)(d->C / d->H));
     const float* logits = (const float*)(sv + L.logits);
     float* dxmid = (float*)(sc + S.dxmid);
 
-    // (f32: the split TN kernel needs N, K and the row strides -- C, 2C, 3C, hidden -- to be multiples of 4; C = 64 H always is, a hidden width that is not falls
+    // (f32: the split TN kernel needs N, K and the row strides -- C, 2C, 3C, hidden -- to be multiples of 4; C = D H (D a multiple of 32) always is, a hidden width that is not falls
     //  through to the exact transposed-copy path below, never less accurate than asked for, as maed_gemm_nt does)
     if (d->impl != MAED_IMPL_VALU && (dt == MAED_BF16 || (maed_x3_planes() && d->hidden % 4 == 0))) {
         // ---- bf16, and f32 in the split-bf16 matmul mode: weight gradients straight from the row-major operands (maed_gemm_tn_wgrad), no transposed copies ----
@@ -524,9 +549,8 @@ extern "C" int maed_ste_block_bwd(const maed_block_dims* d, const maed_block_par
             MAED_PROPAGATE(maed_st_mix_bwd_apply(sc + S.act, logits, sc + S.dmeans, sc + S.dxs, sc + S.dxt, d->F, d->P, C, dt, stream));
         }
         if (ss) MAED_HIP(hipStreamWaitEvent(main_s, ss->ev[63], 0), "ste_block_bwd: stream wait");               // the attention backward overwrites bigA, which the fc1 weight gradient reads
-        PROF(PROF_ATTN_TM_BWD, maed_attn_temporal_bwd(sv + L.qkv, sv + L.xt, sc + S.dxt, (const float*)(sv + L.lse_t), sc + S.bigA, 0, d->F, d->P, d->H, d->T, scale, dt, stream));
-        PROF(PROF_ATTN_SP_BWD, maed_attn_spatial_bwd(sv + L.qkv, sv + L.xs, sc + S.dxs, (const float*)(sv + L.lse_s), sc + S.bigA, 1, d->F, d->P, d->H, scale, dt,
-                                                     MAED_IMPL_AUTO, stream));
+        PROF(PROF_ATTN_TM_BWD, attn_tm_bwd(d, sv + L.qkv, sv + L.xt, sc + S.dxt, (const float*)(sv + L.lse_t), sc + S.bigA, 0, scale, stream));
+        PROF(PROF_ATTN_SP_BWD, attn_sp_bwd(d, sv + L.qkv, sv + L.xs, sc + S.dxs, (const float*)(sv + L.lse_s), sc + S.bigA, 1, scale, MAED_IMPL_AUTO, stream));
         TO_SIDE();
         WGRAD(maed_gemm_tn_wgrad(sc + S.bigA, 3 * C, sv + L.ln1, C, M, 3 * C, C, g->w_qkv, C, g->b_qkv, dmm, wst));
         PROF(PROF_GEMM_DGRAD, maed_gemm_nt(sc + S.bigA, 3 * C, p->wt_qkv, 3 * C, M, C, 3 * C, dmm, MAED_EPI_STORE, nullptr, sc + S.act, C, nullptr, nullptr, 0, 1, gi, stream));
@@ -562,9 +586,9 @@ extern "C" int maed_ste_block_bwd(const maed_block_dims* d, const maed_block_par
     PROF(PROF_GEMM_WGRAD, wgrad(sc + S.dlogT, sc + S.meansT, 2 * C, 2 * C, Fp, g->w_ts, *d, stream));
     MAED_PROPAGATE(maed_gemm_nt(sc + S.dlog, 2 * C, p->wt_ts, 2 * C, d->F, 2 * C, 2 * C, dt, MAED_EPI_STORE, nullptr, sc + S.dmeans, 2 * C, nullptr, nullptr, 0, 1, gi, stream));
     MAED_PROPAGATE(maed_st_mix_bwd_apply(sc + S.act, logits, sc + S.dmeans, sc + S.dxs, sc + S.dxt, d->F, d->P, C, dt, stream));
-    PROF(PROF_ATTN_TM_BWD, maed_attn_temporal_bwd(sv + L.qkv, sv + L.xt, sc + S.dxt, (const float*)(sv + L.lse_t), sc + S.bigA, 0, d->F, d->P, d->H, d->T, scale, dt, stream));
-    PROF(PROF_ATTN_SP_BWD, maed_attn_spatial_bwd(sv + L.qkv, sv + L.xs, sc + S.dxs, (const float*)(sv + L.lse_s), sc + S.bigA, 1, d->F, d->P, d->H, scale, dt,
-                                         d->impl == MAED_IMPL_VALU ? MAED_IMPL_VALU : MAED_IMPL_AUTO, stream));
+    PROF(PROF_ATTN_TM_BWD, attn_tm_bwd(d, sv + L.qkv, sv + L.xt, sc + S.dxt, (const float*)(sv + L.lse_t), sc + S.bigA, 0, scale, stream));
+    PROF(PROF_ATTN_SP_BWD, attn_sp_bwd(d, sv + L.qkv, sv + L.xs, sc + S.dxs, (const float*)(sv + L.lse_s), sc + S.bigA, 1, scale,
+                                               d->impl == MAED_IMPL_VALU ? MAED_IMPL_VALU : MAED_IMPL_AUTO, stream));
     MAED_PROPAGATE(maed_transpose_cast(sc + S.bigA, dt, 3 * C, M, 3 * C, sc + S.bigT, Mp, nullptr, 0, g->b_qkv, dt, stream));
     MAED_PROPAGATE(maed_transpose_cast(sv + L.ln1, dt, C, M, C, sc + S.xT, Mp, nullptr, 0, nullptr, dt, stream));
     PROF(PROF_GEMM_WGRAD, wgrad(sc + S.bigT, sc + S.xT, 3 * C, C, Mp, g->w_qkv, *d, stream));

@@ -89,7 +89,9 @@ def set_float32_backward_precision(mode):
     driver reads it); MAED_F32_BWD=bf16x1 in the environment sets the initial value.
     "bf16" (round 5): the backward is the bf16 MODE's, on bf16 twins of the saved activations (STE blocks: maed_ste_block_fwd_twin; backbone: the bf16 autograd graph
     over fp32 shadow tensors, maed_amd/resnetv2.py) -- bf16 operand traffic and the bf16 kernels instead of one-plane products on fp32 operands; whatever keeps fp32
-    operands in its backward (the few GEMMs outside the blocks and the backbone) uses one plane."""
+    operands in its backward (the few GEMMs outside the blocks and the backbone) uses one plane.
+    Head sizes other than 64 (C / H in 32, 96, 128): the twin forward (maed_ste_block_fwd_twin) is not extended to them -- under "bf16" such a block takes the forward's
+    engine for its backward (GEMMs per MAED_OPT_F32_BWD_X1 as under "bf16x1"), and its attention contractions stay on the exact fp32 kernels in every fp32 mode."""
     assert mode in (None, "same", "bf16x1", "bf16"), mode
     L.set_option(L.OPT_F32_BWD_X1, int(mode in ("bf16x1", "bf16")))
     _BWD_TWIN[0] = mode == "bf16"
@@ -440,9 +442,43 @@ def transpose_cast(x, out_dtype, want_t=True, want_c=False, colsum=None, pad_to=
     return out_t, out_c
 
 
+def head_dim(C_, H):
+    """C / H, checked against the head sizes the attention kernels cover (L.HEAD_DIMS)"""
+    D = C_ // H
+    if D * H != C_ or D not in L.HEAD_DIMS:
+        raise NotImplementedError(f"head size {C_}/{H}: the attention kernels cover head sizes {L.HEAD_DIMS}")
+    return D
+
+
+def attn_seq_fwd(qkv, H, groups, length, inner, impl=L.IMPL_AUTO):
+    """maed_attn_seq_fwd (include/maed_hip.h): attention over `groups` x `inner` x H strided sequences of `length` token rows of qkv (F, P, 3C), any supported head
+    size -- spatial: (F, P, 1), coupling: (F/T, T*P, 1), temporal: (F/T, T, P).  Returns o (F, P, C) and lse (F, H, P) in the 64-wide entry points' layouts."""
+    F_, P, C3 = qkv.shape
+    C_ = C3 // 3
+    assert groups * length * inner == F_ * P, (groups, length, inner, qkv.shape)
+    qkv = _c(qkv)
+    o = torch.empty(F_, P, C_, dtype=qkv.dtype, device=qkv.device)
+    lse = torch.empty(F_, H, P, dtype=torch.float32, device=qkv.device)
+    D = head_dim(C_, H)
+    check(L.lib().maed_attn_seq_fwd(_p(qkv), _p(o), _p(lse), groups, length, inner, H, D, 1.0 / math.sqrt(D), dt_code(qkv.dtype), impl, _stream()), "attn_seq_fwd")
+    return o, lse
+
+
+def attn_seq_bwd(qkv, o, d_o, lse, H, groups, length, inner, dqkv=None, accumulate=False, impl=L.IMPL_AUTO):
+    F_, P, C3 = qkv.shape
+    assert groups * length * inner == F_ * P, (groups, length, inner, qkv.shape)
+    dqkv = torch.empty_like(qkv) if dqkv is None else dqkv
+    D = head_dim(C3 // 3, H)
+    check(L.lib().maed_attn_seq_bwd(_p(_c(qkv)), _p(_c(o)), _p(_c(d_o)), _p(lse), _p(dqkv), int(accumulate), groups, length, inner, H, D, 1.0 / math.sqrt(D),
+                                    dt_code(qkv.dtype), impl, _stream()), "attn_seq_bwd")
+    return dqkv
+
+
 def attn_spatial_fwd(qkv, H, impl=L.IMPL_AUTO):
     F_, P, C3 = qkv.shape
     C_ = C3 // 3
+    if head_dim(C_, H) != 64:       # head sizes 32 / 96 / 128: the head-size-generic kernels (64 keeps its own entry point and dispatch)
+        return attn_seq_fwd(qkv, H, F_, P, 1, impl)
     qkv = _c(qkv)
     o = torch.empty(F_, P, C_, dtype=qkv.dtype, device=qkv.device)
     lse = torch.empty(F_, H, P, dtype=torch.float32, device=qkv.device)
@@ -453,6 +489,8 @@ def attn_spatial_fwd(qkv, H, impl=L.IMPL_AUTO):
 
 def attn_spatial_bwd(qkv, o, d_o, lse, H, dqkv=None, accumulate=False, impl=L.IMPL_AUTO):
     F_, P, C3 = qkv.shape
+    if head_dim(C3 // 3, H) != 64:
+        return attn_seq_bwd(qkv, o, d_o, lse, H, F_, P, 1, dqkv, accumulate, impl)
     dqkv = torch.empty_like(qkv) if dqkv is None else dqkv
     check(L.lib().maed_attn_spatial_bwd(_p(_c(qkv)), _p(_c(o)), _p(_c(d_o)), _p(lse), _p(dqkv), int(accumulate), F_, P, H,
                                         1.0 / math.sqrt(C3 // 3 // H), dt_code(qkv.dtype), impl, _stream()), "attn_spatial_bwd")
@@ -463,6 +501,8 @@ def attn_temporal_fwd(qkv, H, T, prec=None):
     """prec (fp32 only): "bf16x3" = split-bf16 contractions on the matrix cores for this call (one-tile sequences: 32 % T == 0), None = the process-wide mode"""
     F_, P, C3 = qkv.shape
     C_ = C3 // 3
+    if head_dim(C_, H) != 64:       # (fp32: the exact kernels, whatever `prec` or the process-wide mode says -- as for frame counts that do not divide 32)
+        return attn_seq_fwd(qkv, H, F_ // T, T, P)
     qkv = _c(qkv)
     o = torch.empty(F_, P, C_, dtype=qkv.dtype, device=qkv.device)
     lse = torch.empty(F_, H, P, dtype=torch.float32, device=qkv.device)
@@ -473,6 +513,8 @@ def attn_temporal_fwd(qkv, H, T, prec=None):
 
 def attn_temporal_bwd(qkv, o, d_o, lse, H, T, dqkv=None, accumulate=False, prec=None):
     F_, P, C3 = qkv.shape
+    if head_dim(C3 // 3, H) != 64:
+        return attn_seq_bwd(qkv, o, d_o, lse, H, F_ // T, T, P, dqkv, accumulate)
     dqkv = torch.empty_like(qkv) if dqkv is None else dqkv
     check(L.lib().maed_attn_temporal_bwd(_p(_c(qkv)), _p(_c(o)), _p(_c(d_o)), _p(lse), _p(dqkv), int(accumulate), F_, P, H, T,
                                          1.0 / math.sqrt(C3 // 3 // H), mm_code(qkv.dtype, prec), _stream()), "attn_temporal_bwd")
@@ -810,7 +852,8 @@ class STEBlockFn(ReportingFn):
         d = L.BlockDims(*dims)
         y = torch.empty_like(x)
         # fp32 forward, bf16 twins for the backward (set_float32_backward_precision("bf16")): the arena has the bf16 block's layout, the backward its dims
-        twin = block.compute_dtype == torch.float32 and bwd_twin() and ReportingFn.will_run_backward(ctx) and dims[7] != L.IMPL_VALU and dims[2] % 8 == 0 and dims[5] % 8 == 0
+        twin = block.compute_dtype == torch.float32 and bwd_twin() and ReportingFn.will_run_backward(ctx) and dims[7] != L.IMPL_VALU and dims[2] % 8 == 0 and dims[5] % 8 == 0 \
+            and dims[2] == 64 * dims[3]      # (the twin forward exists for head size 64 only: other head sizes take the forward's engine for their backward)
         if twin:
             dims = dims[:6] + (BF16,) + dims[7:]
             d16 = L.BlockDims(*dims)

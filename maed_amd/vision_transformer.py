@@ -71,8 +71,8 @@ class Attention(nn.Module):
         super().__init__()
         if st_mode not in ST_MODES:
             raise NotImplementedError(st_mode)       # the reference raises at forward time (:175)
-        if dim != 64 * num_heads:
-            raise NotImplementedError(f"head dim must be 64 (dim={dim}, heads={num_heads})")
+        if dim % num_heads or dim // num_heads not in L.HEAD_DIMS:
+            raise NotImplementedError(f"head size dim/num_heads must be one of {L.HEAD_DIMS} (dim={dim}, heads={num_heads})")
         if qk_scale is not None or attn_drop or proj_drop:
             raise NotImplementedError("qk_scale / attention dropout are not used on the MAED path")
         self.num_heads = num_heads
