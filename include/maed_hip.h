@@ -125,6 +125,10 @@ typedef enum {
     MAED_OPT_CONV3X3_FRAME = 17,   /* maed_conv3x3_fwd (bf16, round 6): feature maps of 129 .. 256 pixels whose frames fill the chip (stage 3 of the R50: 14 x 14, 128 frames x
                                     * 2 column tiles) run on ONE FRAME x 128 channels per workgroup with a three-stage copy ring (one workgroup per CU, no imbalance, the
                                     * weight rows shared by a whole frame): 1 (default); 0 = the 128 x 128 tiles of rounds 2-5 (A/B knob); 2 = whenever the shape allows, however few frames (tests) */
+    MAED_OPT_CONV3X3_WGRAD_TAPS = 18, /* bf16 3x3 weight gradients at channel counts that are multiples of 64 on the tap-resident kernel (maed_conv3x3_wgrad_taps;
+                                    * the 64 -> 64 stride-1 shape of MAED_OPT_CONV3X3_ROWS_WGS keeps its row kernel): 1 (default) = shapes of >= 4096 output pixels
+                                    * and the ones the general kernel cannot take (pixel count no multiple of 64); 0 = the general TN kernels (A/B knob);
+                                    * 2 = whenever the shape allows, however small (tests); 2 + n = the same with the work items cut into n chunks (tests) */
     MAED_OPT_COUNT
 } maed_option;
 /* Check that `device` (a HIP device ordinal) is one this library was built for (gfx950: MI355X).  MAED_OK, or MAED_ERR_UNSUPPORTED with the device's
@@ -541,6 +545,17 @@ int maed_stem_input(const float* x, void* y, int N, int C, int H, int W, int pad
  * NULL: the workgroups add into dW with atomics (slower: every workgroup adds onto the same 147 KB). */
 int maed_conv3x3_wgrad_rows64_scratch_floats(int F, int H, int W, int Cin, int Cout);
 int maed_conv3x3_wgrad_rows64(const void* dy, const void* x, float* dW, void* scratch, int F, int H, int W, int dtype, void* stream);
+
+/* Weight gradient of the 3x3 SAME convolution, stride 1 or 2, at channel counts that are multiples of 64, with all nine taps resident (csrc/conv3x3_rows.hip,
+ * MAED_OPT_CONV3X3_WGRAD_TAPS): a workgroup owns a 64 (co) x 9 x 64 (ci) block of dW and walks work items of R image rows; maed_conv3x3_wgrad and
+ * maed_conv3x3_s2_wgrad take the same kernel with atomics for the shapes maed_conv3x3_wgrad_taps_scratch_floats answers > 0 for.
+ *   dy (F, Ho, Wo, Cout), x (F, H, W, Cin) channels_last bf16, 16-B aligned; stride 1: Ho = H, Wo = W, pads ignored; stride 2: input pixel 2 o + k - pad
+ *   zero_page: >= 16 bytes of zeros, 16-B aligned (the source of every border / padding slot)
+ *   dW (Cout, 3, 3, Cin) fp32, ACCUMULATED;  scratch: maed_conv3x3_wgrad_taps_scratch_floats(...) fp32 elements (0 = shape not covered by the option's present
+ *   value) for one partial dW per chunk of work items (plain stores + one reduction pass); NULL: the workgroups add into dW with atomics. */
+int maed_conv3x3_wgrad_taps_scratch_floats(int F, int H, int W, int Cin, int Cout, int stride, int Ho, int Wo);
+int maed_conv3x3_wgrad_taps(const void* dy, const void* x, const void* zero_page, float* dW, void* scratch, int F, int H, int W, int Cin, int Cout, int stride,
+                            int pad_top, int pad_left, int Ho, int Wo, int dtype, void* stream);
 
 int maed_stem7x7s2_supported(int H, int W);
 int maed_stem7x7s2_fwd(const void* xp, const void* w, void* wimg, void* y, double* gn_sums, int F, int H, int W, int dtype, void* stream);

@@ -20,7 +20,7 @@ IMPL_MFMA_LONG = 5      # attention only: K/V-tiled long-sequence kernels
 IMPL_MFMA_SK = 10      # gemm_nt only: persistent K-stream kernel (csrc/gemm_sk.hip)
 IMPL_X3, IMPL_X6, IMPL_X1 = 7, 8, 9  # MAED_F32 matrix products on the bf16 matrix cores (split-bf16: 3 / 6 MFMAs per product), csrc/gemm_x3.hip
 (OPT_F32_MATMUL, OPT_SIDE_STREAM, OPT_TN_TARGET_WGS, OPT_ABLATE, OPT_GN_BWD_ONEPASS, OPT_F32_BWD_X1, OPT_ST_FUSED, OPT_CONV3X3_ROWS_WGS, OPT_STEM_WGRAD_WGS,
- OPT_LBS_FRAMES, OPT_TN_DMA, OPT_X3_PLANES, OPT_X3_PLANES_LN, OPT_SK, OPT_SK_GRID, OPT_TN_SK, OPT_CONV3X3_NARROW_WGS, OPT_CONV3X3_FRAME) = range(18)   # maed_option (include/maed_hip.h)
+ OPT_LBS_FRAMES, OPT_TN_DMA, OPT_X3_PLANES, OPT_X3_PLANES_LN, OPT_SK, OPT_SK_GRID, OPT_TN_SK, OPT_CONV3X3_NARROW_WGS, OPT_CONV3X3_FRAME, OPT_CONV3X3_WGRAD_TAPS) = range(19)   # maed_option (include/maed_hip.h)
 
 vp, i64, i32, f32 = C.c_void_p, C.c_int64, C.c_int, C.c_float
 
@@ -158,6 +158,8 @@ SIGNATURES = {
     "maed_stem_input": (i32, [vp, vp, i32, i32, i32, i32, i32, i32, i32, i32, i32, i32, vp]),
     "maed_conv3x3_wgrad_rows64_scratch_floats": (i32, [i32, i32, i32, i32, i32]),
     "maed_conv3x3_wgrad_rows64": (i32, [vp, vp, vp, vp, i32, i32, i32, i32, vp]),
+    "maed_conv3x3_wgrad_taps_scratch_floats": (i32, [i32, i32, i32, i32, i32, i32, i32, i32]),
+    "maed_conv3x3_wgrad_taps": (i32, [vp, vp, vp, vp, vp, i32, i32, i32, i32, i32, i32, i32, i32, i32, i32, i32, vp]),
     "maed_stem7x7s2_supported": (i32, [i32, i32]),
     "maed_stem7x7s2_fwd": (i32, [vp, vp, vp, vp, vp, i32, i32, i32, i32, vp]),
     "maed_stem7x7s2_wgrad_scratch_floats": (i32, [i32, i32, i32]),
@@ -235,6 +237,7 @@ _OPTIONS = {
     OPT_SK: int(os.environ.get("MAED_SK", "1")),                         # A/B knob: 0 = bf16 NT GEMMs on the per-tile kernels of rounds 1-5; 1 = persistent K-stream kernel by heuristic; 2 / 3 = forced
     OPT_SK_GRID: int(os.environ.get("MAED_SK_GRID", "0")),
     OPT_CONV3X3_FRAME: int(os.environ.get("MAED_CONV3X3_FRAME", "1")),              # 0: the stage-3 3x3 convolutions on 128 x 128 tiles (A/B knob)
+    OPT_CONV3X3_WGRAD_TAPS: int(os.environ.get("MAED_CONV3X3_WGRAD_TAPS", "1")),   # 0: the stage-2 / stage-3 3x3 weight gradients on the general TN kernels (A/B knob)
     OPT_CONV3X3_NARROW_WGS: int(os.environ.get("MAED_CONV3X3_NARROW_WGS", "0")),   # 3x3 convolutions whose 128 x 128 grid is smaller than this take 128 x 64 tiles
     OPT_TN_SK: int(os.environ.get("MAED_TN_SK", "1")),                   # A/B knob: 0 = weight-gradient GEMMs on the split-M kernels with closing atomics (rounds 1-5)               # workgroups of the persistent kernel (0 = one per CU)
     OPT_X3_PLANES_LN: int(os.environ.get("MAED_X3_PLANES_LN", "0")),     # 1: ... and the two LayerNorm outputs as planes, qkv / fc1 on the plane kernel (measured neutral); 0 = fc2 only

@@ -159,3 +159,228 @@ extern "C" int maed_conv3x3_wgrad_rows64(const void* dy, const void* x, float* d
     ProfScope prof__(PROF_TN_CONV, stream, 2.0 * (double)F * H * W * 64 * 576, 2.0 * (double)F * H * W * 128 + 36.0 * 64 * 64);
     return maed_conv3x3_wgrad_rows64_launch(dy, x, dW, scratch, F, H, W, (hipStream_t)stream);
 }
+
+// ---- Tap-resident weight gradient for channel counts that are multiples of 64 (the conv2 of the stage-2 / stage-3 bottlenecks: 128 -> 128 at 28 x 28, 256 -> 256 at
+// 14 x 14, and the two stride-2 ones), MAED_OPT_CONV3X3_WGRAD_TAPS.  The row kernel above, generalised:
+//   * a workgroup owns a 64 (co) x 9 (tap) x 64 (ci) block of dW (wave = tap, the same four 32 x 32 accumulators) -- grid.y walks the co x ci blocks, grid.x chunks
+//     of work items; the 64-channel slice of a pixel is 128 contiguous bytes of the channels-last row, so the LDS images and the transposing reads stay as they are.
+//   * a work item is R consecutive output rows of one frame as ONE linear run of pixel slots with pitch P: the dy image has P - Wo zero slots behind every row, the
+//     x image is the matching window of input rows framed by zero pixels, and a tap is a constant slot offset (stride 1: P = W + 2, tap = ky P + kx;  stride 2:
+//     P = Wo + 1, the input rows are split by row and column parity into four phase images of XP slots each, tap = ((ky & 1) 2 + (kx & 1)) XP + (ky >> 1) P +
+//     (kx >> 1)).  K is the run in 16-slot steps.  Items never straddle a frame; rows above / below the image, a ragged last item and the tail of the last k-step are
+//     zero slots like the borders.
+//   * EVERY slot an item reads is written by that item's copies: each lane of a copy instruction picks its own 16-byte source -- a pixel chunk or the page of zeros --
+//     so no row length has to fill a 64-lane instruction, nothing is zeroed up front, and no lane is predicated.  The lane -> (row, column) map does not depend on the
+//     item and is computed once per lane.  Chunk c of slot s is stored at c ^ 4 ((s >> 1) & 1), as above.
+//   * two or three stages of (dy image + x image); the copies of item g + 1 (g + 2) are issued right behind the barrier that frees the stage of item g - 1.
+#define T9_THREADS 576
+#define T9_MAXDY 4                        // copy instructions per wave and item for the dy image: 36 x 8 = 288 slots
+#define T9_MAXX 8                         // ... for the x image(s): 576 slots
+#define T9_MAX_SLOTS 1280                 // dy + x slots of all stages: 160 KB
+
+struct TapsGeo {
+    int H, W, Ho, Wo, Cin, Cout, s2, pt, pl;
+    int R, ipf, n_items;                  // output rows per item, items per frame, items
+    int P, ksteps, DS, XP, XS, nst;       // slot pitch, 16-slot steps, dy slots, slots per phase image (stride 2), x slots, stages
+    int per, chunks, cib, cob;            // items per workgroup, grid.x, ci / co blocks
+};
+
+#define T9_WAIT(n_) switch (n_) { case 1: MAED_WAIT_VMCNT(1); break; case 2: MAED_WAIT_VMCNT(2); break; case 3: MAED_WAIT_VMCNT(3); break; case 4: MAED_WAIT_VMCNT(4); break; \
+    case 5: MAED_WAIT_VMCNT(5); break; case 6: MAED_WAIT_VMCNT(6); break; case 7: MAED_WAIT_VMCNT(7); break; case 8: MAED_WAIT_VMCNT(8); break; case 9: MAED_WAIT_VMCNT(9); break; \
+    case 10: MAED_WAIT_VMCNT(10); break; case 11: MAED_WAIT_VMCNT(11); break; case 12: MAED_WAIT_VMCNT(12); break; default: MAED_WAIT_VMCNT0(); }
+
+__global__ __launch_bounds__(T9_THREADS, 1) void conv3x3_wgrad_taps_kernel(const bf16* __restrict__ dy, const bf16* __restrict__ x, const bf16* __restrict__ zero,
+                                                                             float* __restrict__ dW, float* __restrict__ partial, TapsGeo g) {
+    MAED_DYN_SHARED(unsigned short, smem);
+    const int tid = threadIdx.x, lane = tid & 63, tap = __builtin_amdgcn_readfirstlane(tid >> 6), l31 = lane & 31, hi = lane >> 5, i16 = lane & 15;
+    const int ky = tap / 3, kx = tap - 3 * ky;
+    const int i0 = blockIdx.x * g.per;
+    int i1 = i0 + g.per;
+    if (i1 > g.n_items) i1 = g.n_items;
+    if (i0 >= i1) return;
+    const int cb = blockIdx.y / g.cib, ib = blockIdx.y - cb * g.cib;
+    const int P = g.P, ndi = g.DS >> 3, nxi = g.XS >> 3, stage_elems = (g.DS + g.XS) * 64;
+
+    // source of this lane's 16 bytes in copy instruction tap + 9 q of an item: row relative to the item's first row (1 << 20: a slot that is zero in every item) and
+    // byte offset relative to that row's start; position (slot, chunk) = (8 j + (lane >> 3), lane & 7) of instruction j
+    int dyrel[T9_MAXDY], dyrow[T9_MAXDY], xrel[T9_MAXX], xrow[T9_MAXX];
+    int n_mine = 0;
+#pragma unroll
+    for (int q = 0; q < T9_MAXDY; ++q) {
+        const int s = (tap + 9 * q) * 8 + (lane >> 3), r = s / P, c = s - r * P, ch = (lane & 7) ^ (((s >> 1) & 1) << 2);
+        dyrow[q] = (c < g.Wo && r < g.R) ? r : (1 << 20);
+        dyrel[q] = ((r * g.Wo + c) * g.Cout + cb * 64) * 2 + ch * 16;
+        n_mine += (tap + 9 * q < ndi) ? 1 : 0;
+    }
+#pragma unroll
+    for (int q = 0; q < T9_MAXX; ++q) {
+        const int u = (tap + 9 * q) * 8 + (lane >> 3), ch = (lane & 7) ^ (((u >> 1) & 1) << 2);
+        int ro, col;
+        bool ok;
+        if (!g.s2) { const int rr = u / P; ro = rr - 1; col = u - rr * P - 1; ok = rr < g.R + 2; }
+        else { const int ph = u / g.XP, v = u - ph * g.XP, rr = v / P; ro = 2 * rr + (ph >> 1); col = 2 * (v - rr * P) + (ph & 1) - g.pl; ok = rr < g.R + 1; }
+        xrow[q] = (ok && (unsigned)col < (unsigned)g.W) ? ro : (1 << 20);
+        xrel[q] = ((ro * g.W + col) * g.Cin + ib * 64) * 2 + ch * 16;
+        n_mine += (tap + 9 * q < nxi) ? 1 : 0;
+    }
+    n_mine = __builtin_amdgcn_readfirstlane(n_mine);
+#define T9_ISSUE(it_, st_) { const int it__ = (it_), f__ = it__ / g.ipf, y0__ = (it__ - f__ * g.ipf) * g.R, yb__ = g.s2 ? 2 * y0__ - g.pt : y0__; \
+        unsigned short* const sb__ = smem + (st_) * stage_elems; \
+        const char* const dyb__ = (const char*)dy + ((int64_t)f__ * g.Ho + y0__) * g.Wo * g.Cout * 2; \
+        const char* const xb__ = (const char*)x + ((int64_t)f__ * g.H + yb__) * g.W * g.Cin * 2; \
+        _Pragma("unroll") for (int q = 0; q < T9_MAXDY; ++q) if (tap + 9 * q < ndi) { \
+            const char* s__ = (unsigned)(y0__ + dyrow[q]) < (unsigned)g.Ho ? dyb__ + dyrel[q] : (const char*)zero; \
+            MAED_LDS_DMA16_PTR(s__, sb__ + (tap + 9 * q) * 512); } \
+        _Pragma("unroll") for (int q = 0; q < T9_MAXX; ++q) if (tap + 9 * q < nxi) { \
+            const char* s__ = (unsigned)(yb__ + xrow[q]) < (unsigned)g.H ? xb__ + xrel[q] : (const char*)zero; \
+            MAED_LDS_DMA16_PTR(s__, sb__ + g.DS * 64 + (tap + 9 * q) * 512); } }
+
+    f32x16_t acc[2][2];
+#pragma unroll
+    for (int r = 0; r < 16; ++r) { acc[0][0][r] = 0.f; acc[0][1][r] = 0.f; acc[1][0][r] = 0.f; acc[1][1][r] = 0.f; }
+    // transposing reads as in the row kernel; the x operand's slot is the dy slot + the tap's offset (bit 1 of a slot is unchanged by + 8 and + 16 s)
+    const int toff = g.s2 ? ((ky & 1) * 2 + (kx & 1)) * g.XP + (ky >> 1) * P + (kx >> 1) : ky * P + kx;
+    const int prow = 4 * hi + (i16 >> 2), pcol = (lane & 16) + 4 * (i16 & 3);
+    const int swa = ((prow >> 1) & 1) << 2, swb = (((prow + toff) >> 1) & 1) << 2;
+    const int a_off0 = prow * 64 + ((((pcol >> 3) ^ swa) << 3) | (pcol & 7)), a_off1 = prow * 64 + (((((pcol + 32) >> 3) ^ swa) << 3) | (pcol & 7));
+    const int b_off0 = (prow + toff) * 64 + ((((pcol >> 3) ^ swb) << 3) | (pcol & 7)), b_off1 = (prow + toff) * 64 + (((((pcol + 32) >> 3) ^ swb) << 3) | (pcol & 7));
+
+    const int ahead = g.nst - 1;                                          // items whose copies run ahead of the one in use: 1 or 2
+    T9_ISSUE(i0, 0);
+    if (ahead > 1 && i0 + 1 < i1) T9_ISSUE(i0 + 1, 1);
+    int st = 0;                                                           // stage of item it
+    for (int it = i0; it < i1; ++it) {
+        // item it's copies are complete once only the younger item's (n_mine per wave, when it was issued) are outstanding
+        if (ahead > 1 && it + 1 < i1) { T9_WAIT(n_mine) } else { MAED_WAIT_VMCNT0(); }
+        __syncthreads();                 // item it's images have landed for every wave; nobody still reads item it - 1's stage
+        if (it + ahead < i1) { int sn = st + ahead; if (sn >= g.nst) sn -= g.nst; T9_ISSUE(it + ahead, sn); }
+        const unsigned short* da = smem + st * stage_elems;
+        const unsigned short* xb = da + g.DS * 64;
+        // two fragment sets: the reads of k-step s + 1 are issued before the MFMAs of k-step s (a wave shares its SIMD with at most two others: the LDS round trip
+        // of a step read and multiplied in turn stayed exposed)
+        union Frag { bf16x8_t v; uint2 u[2]; };
+        Frag pa0, pa1, pb0, pb1, qa0, qa1, qb0, qb1;
+#define T9_FRAG(dst_, base_, s_, off_) { auto lo__ = MAED_DS_READ_TR16((base_) + (s_) * 1024 + (off_)); auto hi__ = MAED_DS_READ_TR16((base_) + (s_) * 1024 + 512 + (off_)); \
+            __builtin_memcpy(&dst_.u[0], &lo__, 8); __builtin_memcpy(&dst_.u[1], &hi__, 8); }
+#define T9_LOAD(p_, s_) { T9_FRAG(p_##a0, da, s_, a_off0) T9_FRAG(p_##a1, da, s_, a_off1) T9_FRAG(p_##b0, xb, s_, b_off0) T9_FRAG(p_##b1, xb, s_, b_off1) }
+#define T9_MFMA(p_) { acc[0][0] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(p_##a0.v, p_##b0.v, acc[0][0], 0, 0, 0); \
+            acc[0][1] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(p_##a0.v, p_##b1.v, acc[0][1], 0, 0, 0); \
+            acc[1][0] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(p_##a1.v, p_##b0.v, acc[1][0], 0, 0, 0); \
+            acc[1][1] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(p_##a1.v, p_##b1.v, acc[1][1], 0, 0, 0); }
+        T9_LOAD(p, 0)
+        int s = 0;
+        for (; s + 2 <= g.ksteps; s += 2) {
+            T9_LOAD(q, s + 1)
+            __builtin_amdgcn_sched_barrier(0);      // (hipcc sinks the reads below the MFMAs otherwise)
+            T9_MFMA(p)
+            __builtin_amdgcn_sched_barrier(0);
+            { const int sn = s + 2 < g.ksteps ? s + 2 : s; T9_LOAD(p, sn) }      // (branch-free: past the end it reads a step again; a branch here lets hipcc sink the reads)
+            __builtin_amdgcn_sched_barrier(0);
+            T9_MFMA(q)
+            __builtin_amdgcn_sched_barrier(0);
+        }
+        if (s < g.ksteps) T9_MFMA(p)
+#undef T9_MFMA
+#undef T9_LOAD
+#undef T9_FRAG
+        if (++st == g.nst) st = 0;
+    }
+#undef T9_ISSUE
+    // D[co][ci] as in the row kernel; dW (Cout, 9, Cin).  With `partial` the workgroup stores its block with plain stores into the partial dW of its chunk
+    // (grid.x of them, summed by wgrad_slots_reduce_kernel); without, it adds into dW with atomics.
+    const size_t ld = (size_t)9 * g.Cin;
+    float* const base = (partial ? partial + (size_t)blockIdx.x * g.Cout * ld : dW) + (size_t)cb * 64 * ld + tap * g.Cin + ib * 64;
+#pragma unroll
+    for (int a = 0; a < 2; ++a)
+#pragma unroll
+        for (int bt = 0; bt < 2; ++bt) {
+            float* d = base + 32 * bt + l31;
+#pragma unroll
+            for (int r = 0; r < 16; ++r) {
+                float* e = d + (size_t)(32 * a + (r & 3) + 8 * (r >> 2) + 4 * hi) * ld;
+                if (partial) *e = acc[a][bt][r]; else atomicAdd(e, acc[a][bt][r]);
+            }
+        }
+}
+
+// geometry of a launch; false: the shape (or the option's value) leaves it to the general kernels
+static bool taps_geo(int F, int H, int W, int Cin, int Cout, int stride, int pt, int pl, int Ho, int Wo, TapsGeo* out) {
+    const int opt = maed_opt(MAED_OPT_CONV3X3_WGRAD_TAPS);
+    if (opt <= 0 || F < 1 || H < 1 || W < 1 || Ho < 1 || Wo < 1 || Cin < 64 || Cout < 64 || Cin % 64 || Cout % 64) return false;
+    if (stride == 1) { if (Ho != H || Wo != W || maed_conv3x3_wgrad_rows64_ok(F, H, W, Cin, Cout)) return false; }
+    else if (stride == 2) { if (Ho != (H + 1) / 2 || Wo != (W + 1) / 2 || pt < 0 || pt > 1 || pl < 0 || pl > 1) return false; }
+    else return false;
+    if ((int64_t)H * W * Cin * 2 >= (1ll << 30) || (int64_t)Ho * Wo * Cout * 2 >= (1ll << 30) || (int64_t)Cout * 9 * Cin >= (1ll << 28)) return false;
+    const int64_t M = (int64_t)F * Ho * Wo;
+    if (opt == 1 && M < 4096 && M % 64 == 0) return false;               // small launches the general kernel can take stay there
+    TapsGeo g{};
+    g.H = H; g.W = W; g.Ho = Ho; g.Wo = Wo; g.Cin = Cin; g.Cout = Cout; g.s2 = stride == 2; g.pt = pt; g.pl = pl;
+    g.P = g.s2 ? Wo + 1 : Wo + 2;
+    // the most rows per item whose images fit the copy maps and two stages of LDS, then evened out over the frame
+    int rmax = 0;
+    for (int R = 1; R <= Ho; ++R) {
+        const int DS = (R * g.P + 15) / 16 * 16, XP = (DS + g.P + 1 + 7) / 8 * 8, XS = g.s2 ? 4 * XP : (DS + 2 * g.P + 2 + 7) / 8 * 8;
+        if (DS > T9_MAXDY * 72 || XS > T9_MAXX * 72 || 2 * (DS + XS) > T9_MAX_SLOTS) break;
+        rmax = R;
+    }
+    if (rmax == 0) return false;
+    g.ipf = (Ho + rmax - 1) / rmax;
+    g.R = (Ho + g.ipf - 1) / g.ipf;
+    g.ipf = (Ho + g.R - 1) / g.R;
+    if ((int64_t)F * g.ipf >= (1ll << 30)) return false;
+    g.n_items = F * g.ipf;
+    g.DS = (g.R * g.P + 15) / 16 * 16; g.ksteps = g.DS / 16;
+    g.XP = (g.DS + g.P + 1 + 7) / 8 * 8;
+    g.XS = g.s2 ? 4 * g.XP : (g.DS + 2 * g.P + 2 + 7) / 8 * 8;
+    g.nst = 3 * (g.DS + g.XS) <= T9_MAX_SLOTS ? 3 : 2;
+    g.cib = Cin / 64; g.cob = Cout / 64;
+    if ((int64_t)g.cib * g.cob > 65535) return false;
+    // workgroups: one per CU when the launch has the GPU to itself; beside the main stream (the weight gradients' side stream) a quarter of them -- a workgroup holds
+    // most of a CU's LDS and registers, so a full grid shuts the main stream's kernels out for the length of the launch: 256 workgroups measured no step-time gain
+    // over the general kernel, 128 / 96 / 64 measured -0.11 / -0.23 / -0.29 ms per cfg3 step (profiles/conv3x3_wgrad_taps_ab.txt)
+    const int wgs = maed_opt(MAED_OPT_SIDE_STREAM) ? 64 : 256;
+    int chunks = opt > 2 ? opt - 2 : (wgs + g.cib * g.cob - 1) / (g.cib * g.cob);
+    if (chunks > g.n_items) chunks = g.n_items;
+    g.per = (g.n_items + chunks - 1) / chunks;
+    g.chunks = (g.n_items + g.per - 1) / g.per;
+    *out = g;
+    return true;
+}
+
+bool maed_conv3x3_wgrad_taps_ok(int F, int H, int W, int Cin, int Cout, int stride, int pad_top, int pad_left, int Ho, int Wo) {
+    TapsGeo g;
+    return taps_geo(F, H, W, Cin, Cout, stride, pad_top, pad_left, Ho, Wo, &g);
+}
+
+int maed_conv3x3_wgrad_taps_launch(const void* dy, const void* x, const void* zero_page, float* dW, void* scratch, int F, int H, int W, int Cin, int Cout, int stride,
+                                   int pad_top, int pad_left, int Ho, int Wo, hipStream_t stream) {
+    TapsGeo g;
+    if (!taps_geo(F, H, W, Cin, Cout, stride, pad_top, pad_left, Ho, Wo, &g)) { maed_set_error("conv3x3_wgrad_taps: shape not covered"); return MAED_ERR_SHAPE; }
+    static bool attr_set = false;
+    if (!attr_set) { (void)hipFuncSetAttribute((const void*)conv3x3_wgrad_taps_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024); attr_set = true; }
+    const size_t lds_bytes = (size_t)g.nst * (g.DS + g.XS) * 128;
+    hipLaunchKernelGGL(conv3x3_wgrad_taps_kernel, dim3(g.chunks, g.cib * g.cob), dim3(T9_THREADS), lds_bytes, stream, (const bf16*)dy, (const bf16*)x,
+                       (const bf16*)zero_page, dW, (float*)scratch, g);
+    if (scratch) maed_wgrad_slots_reduce((const float*)scratch, dW, g.chunks, Cout * 9 * Cin, stream);
+    MAED_CHECK_LAUNCH("conv3x3_wgrad(taps)");
+    return MAED_OK;
+}
+
+extern "C" int maed_conv3x3_wgrad_taps_scratch_floats(int F, int H, int W, int Cin, int Cout, int stride, int Ho, int Wo) {
+    TapsGeo g;
+    if (!taps_geo(F, H, W, Cin, Cout, stride, 0, 0, Ho, Wo, &g)) return 0;
+    const int64_t n = (int64_t)g.chunks * Cout * 9 * Cin;
+    return n < (1ll << 31) ? (int)n : 0;
+}
+
+extern "C" int maed_conv3x3_wgrad_taps(const void* dy, const void* x, const void* zero_page, float* dW, void* scratch, int F, int H, int W, int Cin, int Cout,
+                                       int stride, int pad_top, int pad_left, int Ho, int Wo, int dtype, void* stream) {
+    MAED_CHECK_ARG(dy && x && zero_page && dW, MAED_ERR_ARG, "conv3x3_wgrad_taps: null pointer");
+    MAED_CHECK_ARG(dtype == MAED_BF16, MAED_ERR_UNSUPPORTED, "conv3x3_wgrad_taps: bf16 only (dtype=%d)", dtype);
+    MAED_CHECK_ARG(maed_conv3x3_wgrad_taps_ok(F, H, W, Cin, Cout, stride, pad_top, pad_left, Ho, Wo), MAED_ERR_SHAPE,
+                   "conv3x3_wgrad_taps: shape not covered (F=%d H=%d W=%d Cin=%d Cout=%d stride=%d pads %d/%d Ho=%d Wo=%d, option %d)", F, H, W, Cin, Cout, stride,
+                   pad_top, pad_left, Ho, Wo, maed_opt(MAED_OPT_CONV3X3_WGRAD_TAPS));
+    MAED_CHECK_ARG(is_aligned(dy, 16) && is_aligned(x, 16) && is_aligned(zero_page, 16) && is_aligned(scratch, 16), MAED_ERR_ALIGN, "conv3x3_wgrad_taps: 16-B alignment");
+    ProfScope prof__(PROF_TN_CONV, stream, 2.0 * (double)F * Ho * Wo * Cout * 9 * Cin, 2.0 * ((double)F * Ho * Wo * Cout + (double)F * H * W * Cin) + 36.0 * (double)Cout * Cin);
+    return maed_conv3x3_wgrad_taps_launch(dy, x, zero_page, dW, scratch, F, H, W, Cin, Cout, stride, pad_top, pad_left, Ho, Wo, (hipStream_t)stream);
+}

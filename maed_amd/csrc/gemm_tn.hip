@@ -31,6 +31,9 @@ static int tn_remap() { return 1; }     // XCD-aware (split, tile) order: -6...8
 
 bool maed_conv3x3_wgrad_rows64_ok(int F, int H, int W, int Cin, int Cout);                                            // conv3x3_rows.hip
 int maed_conv3x3_wgrad_rows64_launch(const void* dy, const void* x, float* dW, void* scratch, int F, int H, int W, hipStream_t stream);
+bool maed_conv3x3_wgrad_taps_ok(int F, int H, int W, int Cin, int Cout, int stride, int pad_top, int pad_left, int Ho, int Wo);
+int maed_conv3x3_wgrad_taps_launch(const void* dy, const void* x, const void* zero_page, float* dW, void* scratch, int F, int H, int W, int Cin, int Cout, int stride,
+                                   int pad_top, int pad_left, int Ho, int Wo, hipStream_t stream);
 
 #define TN_BM 64      // reduction rows per LDS tile
 #define TN_LD 72      // LDS row stride (elements): 144 B
@@ -400,6 +403,10 @@ extern "C" int maed_conv3x3_wgrad(const void* dy, const void* x, const void* tap
     if (maed_conv3x3_wgrad_rows64_ok(F, H, W, Cin, Cout)) {      // 64 -> 64 channels (stage 1): one image row per work item, all nine taps from LDS (conv3x3_rows.hip)
         MAED_CHECK_ARG(is_aligned(dy, 16) && is_aligned(x, 16), MAED_ERR_ALIGN, "conv3x3_wgrad: 16-B alignment");
         return maed_conv3x3_wgrad_rows64_launch(dy, x, dW, nullptr, F, H, W, (hipStream_t)stream);
+    }
+    if (maed_conv3x3_wgrad_taps_ok(F, H, W, Cin, Cout, 1, 0, 0, H, W)) {      // channel counts that are multiples of 64 (stages 2, 3): R image rows per work item, all nine taps resident
+        MAED_CHECK_ARG(is_aligned(dy, 16) && is_aligned(x, 16) && is_aligned(zero_page, 16), MAED_ERR_ALIGN, "conv3x3_wgrad: 16-B alignment");
+        return maed_conv3x3_wgrad_taps_launch(dy, x, zero_page, dW, nullptr, F, H, W, Cin, Cout, 1, 0, 0, H, W, (hipStream_t)stream);
     }
     MAED_CHECK_ARG(M > 0 && M % TN_BM == 0, MAED_ERR_SHAPE, "conv3x3_wgrad: F*H*W = %lld must be a multiple of 64", (long long)M);
     MAED_CHECK_ARG(Cin % 8 == 0 && Cout % 8 == 0 && Cin < (1 << 20) && W + 1 < (1 << 10), MAED_ERR_SHAPE, "conv3x3_wgrad: need Cin, Cout multiples of 8 (Cin=%d Cout=%d)", Cin, Cout);

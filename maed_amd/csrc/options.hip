@@ -25,6 +25,7 @@ static std::atomic<int> g_opt[MAED_OPT_COUNT] = {
     {1},      // MAED_OPT_TN_SK
     {0},      // MAED_OPT_CONV3X3_NARROW_WGS
     {1},      // MAED_OPT_CONV3X3_FRAME
+    {1},      // MAED_OPT_CONV3X3_WGRAD_TAPS
 };
 
 extern "C" int maed_init(int device) {
@@ -100,6 +101,7 @@ extern "C" int maed_set_option(int key, int value) {
     if (key == MAED_OPT_SK) MAED_CHECK_ARG(value >= 0 && value <= 3, MAED_ERR_ARG, "set_option: MAED_OPT_SK takes 0 (off), 1 (heuristic), 2 (no K cuts) or 3 (always)");
     if (key == MAED_OPT_TN_SK) MAED_CHECK_ARG(value == 0 || value == 1, MAED_ERR_ARG, "set_option: MAED_OPT_TN_SK takes 0 or 1");
     if (key == MAED_OPT_SK_GRID) MAED_CHECK_ARG(value >= 0 && value <= 512, MAED_ERR_ARG, "set_option: MAED_OPT_SK_GRID takes 0 (one workgroup per CU) or a workgroup count <= 512");
+    if (key == MAED_OPT_CONV3X3_WGRAD_TAPS) MAED_CHECK_ARG(value >= 0 && value <= 2 + 65535, MAED_ERR_ARG, "set_option: MAED_OPT_CONV3X3_WGRAD_TAPS takes 0, 1, 2 or 2 + a chunk count");
     g_opt[key].store(value, std::memory_order_relaxed);
     return MAED_OK;
 }

@@ -1526,9 +1526,26 @@ def conv3x3_wgrad(dy, x, out=None, prec=None):
             check(L.lib().maed_conv3x3_wgrad_rows64(_p(dy), _p(x), _p(dW), _p(scratch), N, H, W, dt_code(x.dtype), _stream()), "conv3x3_wgrad_rows64")
             _keep_alive_on_stream(scratch)
             return dW
+        if _conv3x3_wgrad_taps(dy, x, dW, 1, 0, 0):
+            return dW
     check(L.lib().maed_conv3x3_wgrad(_p(dy), _p(x), _p(_tapmask(N, H, W, x.device)), _p(_zero_page(x.device)), _p(dW), N, H, W, I, O,
                                      mm_code(x.dtype, prec), _stream()), "conv3x3_wgrad")
     return dW
+
+
+def _conv3x3_wgrad_taps(dy, x, dW, stride, pad_top, pad_left):
+    """the tap-resident weight-gradient kernel (maed_conv3x3_wgrad_taps: channel counts that are multiples of 64, R image rows per work item) where the library
+    takes the shape: one partial dW per chunk of work items in scratch, summed by a reduction pass.  False: not taken"""
+    N, I, H, W = x.shape
+    O, Ho, Wo = dy.shape[1:]
+    nb = L.lib().maed_conv3x3_wgrad_taps_scratch_floats(N, H, W, I, O, stride, Ho, Wo)
+    if nb <= 0:
+        return False
+    scratch = torch.empty(nb, dtype=torch.float32, device=x.device)
+    check(L.lib().maed_conv3x3_wgrad_taps(_p(dy), _p(x), _p(_zero_page(x.device)), _p(dW), _p(scratch), N, H, W, I, O, stride, pad_top, pad_left, Ho, Wo,
+                                          dt_code(x.dtype), _stream()), "conv3x3_wgrad_taps")
+    _keep_alive_on_stream(scratch)
+    return True
 
 
 _S2_TABLES = {}
@@ -1539,6 +1556,11 @@ def conv3x3_s2_wgrad(dy, x, pad_top, pad_left, out=None):
     The per-output-pixel gather tables depend only on the geometry: cached."""
     N, I, H, W = x.shape
     O, Ho, Wo = dy.shape[1:]
+    if x.dtype == torch.bfloat16 and pad_top in (0, 1) and pad_left in (0, 1):
+        dW = torch.zeros(O, 3, 3, I, dtype=torch.float32, device=x.device) if out is None else out
+        if _conv3x3_wgrad_taps(dy, x, dW, 2, pad_top, pad_left):
+            return dW
+        out = dW
     key = (N, H, W, Ho, Wo, pad_top, pad_left, str(x.device))
     if key not in _S2_TABLES:
         n = (N * Ho * Wo + 63) // 64 * 64
