@@ -9,7 +9,8 @@
 // coalesced read and every reduction is a shuffle tree; one workgroup per frame for the 6890-vertex error.  The 3x3 SVD of the
 // Procrustes step is replaced by what the reference actually consumes, R = V Z U^T with Z fixing det(R)=+1: eigenvectors of
 // K^T K by cyclic Jacobi (fp64, 3x3), U from K V; building both bases right-handed makes Z the identity for every sign
-// convention an SVD routine could pick (see procrustes_rotation), so no branch on det is needed.
+// convention an SVD routine could pick (see procrustes_rotation), so no branch on det is needed.  Where K has rank 1 (one set on a line, J = 2) K V gives
+// one column of U only; the basis is completed there, so R is a proper rotation for every K but K = 0 (scale = 0, S1_hat = mu2).
 #include "common.cuh"
 
 namespace {
@@ -24,6 +25,12 @@ __device__ __forceinline__ double wave_sum_d(double v) {
         v += __hiloint2double(hi, lo);
     }
     return v;
+}
+
+// lane 0's value in every lane.  A wave_sum_d of a product need not be bit-identical across the lanes: the compiler may contract the product into the tree's
+// first add (fma(a, b, partner's rounded product) in one lane, the mirror image in its partner), and the lanes' sums then differ in the last bit.
+__device__ __forceinline__ double wave_first_d(double v) {
+    return __hiloint2double(__builtin_amdgcn_readfirstlane(__double2hiint(v)), __builtin_amdgcn_readfirstlane(__double2loint(v)));
 }
 
 __device__ inline void cross3(const double* a, const double* b, double* c) {
@@ -93,10 +100,20 @@ __device__ inline void procrustes_rotation(const double (&K)[3][3], double (&R)[
         u1[r] = K[r][0] * v1[0] + K[r][1] * v1[1] + K[r][2] * v1[2];
         u2[r] = K[r][0] * v2[0] + K[r][1] * v2[1] + K[r][2] * v2[2];
     }
-    normalize3(u1);
+    const double s1 = normalize3(u1);                              // |K v1|, the largest singular value
     const double d12 = u1[0] * u2[0] + u1[1] * u2[1] + u1[2] * u2[2];
 #pragma unroll
     for (int r = 0; r < 3; ++r) u2[r] -= d12 * u1[r];
+    // rank-1 K: K v2 is zero, or rounding noise of a few eps |K v1| whose direction means nothing -- an SVD returns a full orthonormal U there, so complete
+    // the basis with any unit vector orthogonal to u1 (the rotation is free about u1; the trace, hence the residual, does not depend on the choice).  Below
+    // 1e-12 |K v1| u2 has three digits above that noise at the most, and replacing it costs at most 2e-12 |K v1| of the trace.  K = 0 leaves u1 = u2 = 0: R = 0,
+    // scale = 0, S1_hat = mu2.
+    if (u2[0] * u2[0] + u2[1] * u2[1] + u2[2] * u2[2] <= 1e-24 * s1 * s1) {
+        const double a0 = fabs(u1[0]), a1 = fabs(u1[1]), a2 = fabs(u1[2]);
+        const int m = a0 <= a1 && a0 <= a2 ? 0 : (a1 <= a2 ? 1 : 2);   // the coordinate axis of u1's smallest component: |u1 x axis| >= sqrt(2/3)
+        const double ax[3] = {m == 0 ? 1.0 : 0.0, m == 1 ? 1.0 : 0.0, m == 2 ? 1.0 : 0.0};
+        cross3(u1, ax, u2);
+    }
     normalize3(u2);
     cross3(u1, u2, u3);
 #pragma unroll
@@ -155,8 +172,10 @@ __global__ __launch_bounds__(256) void eval_pose_errors_kernel(const float* __re
 #pragma unroll
     for (int i = 0; i < 3; ++i)
 #pragma unroll
-        for (int j = 0; j < 3; ++j) K[i][j] = wave_sum_d(x1[i] * x2[j]);
-    procrustes_rotation(K, R);                                     // every lane holds the same K: computed redundantly, no broadcast
+        for (int j = 0; j < 3; ++j) K[i][j] = wave_first_d(wave_sum_d(x1[i] * x2[j]));
+    // every lane holds lane 0's K and computes R redundantly.  The lanes must agree to the bit: where two singular values of K coincide (rank 1: both zero) the
+    // eigenvectors of that plane are decided by the last bits of K, and lanes with their own last bits would each rotate their joint about another axis
+    procrustes_rotation(K, R);
     double tr = 0.0;
 #pragma unroll
     for (int i = 0; i < 3; ++i)

@@ -76,7 +76,9 @@ def compute_error_verts(pred_verts, target_verts=None, target_theta=None, smpl=N
 
 
 def batch_compute_similarity_transform_torch(S1, S2):
-    """S1_hat = s R S1 + t closest to S2 (orthogonal Procrustes with scale, det R = +1); (N,J,3) or (N,3,J) like the reference"""
+    """S1_hat = s R S1 + t closest to S2 (orthogonal Procrustes with scale, det R = +1); (N,J,3) or (N,3,J) like the reference.
+    Where the covariance has rank 1 (a set on a line, J = 2) R is one of the optimal rotations -- the residual is the optimum, the aligned
+    points are not unique; S2 constant gives S1_hat = mean(S2); S1 constant (J = 1) gives NaN, as in the reference."""
     if S1.shape[-1] != 3 and S1.shape[1] != 3:
         raise NotImplementedError("only 3-D point sets are evaluated on the MAED path")
     transposed = S1.shape[-1] != 3          # (N,3,J) input; evaluate.py:159 passes (N,J,3)
