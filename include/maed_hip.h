@@ -60,9 +60,13 @@ typedef enum {
     MAED_EPI_ATOMIC_F32 = 4, /* out[f32] += acc  (atomic; weight gradients, split-K allowed)        */
     MAED_EPI_STORE_F32 = 5,  /* out[f32] = acc + bias                                               */
     MAED_EPI_TANH = 6,       /* out[T]   = tanh(acc + bias)                                         */
-    MAED_EPI_ADD = 7         /* out[T]   = aux[T] + acc + bias  (gradient accumulation at a residual fork); out2 != NULL: aux is first
+    MAED_EPI_ADD = 7,        /* out[T]   = aux[T] + acc + bias  (gradient accumulation at a residual fork); out2 != NULL: aux is first
                               * masked by 1 bit per element (bit c & 7 of byte (r * ldaux + c) / 8 = maed_groupnorm_fwd's relu_mask: the
                               * masked residual gradient of a GroupNorm + residual + ReLU is then never materialised) */
+    /* the epilogues of a regularised STE block (maed_gemm_nt_drop only; k / g: the element / frame masks of maed_drop_args) */
+    MAED_EPI_RESID_DROP_F32 = 8,  /* out[f32] = aux[f32] + g(r / group_rows) * k(r, c) * (acc + bias)                     */
+    MAED_EPI_GELU_DROP = 9,       /* out2[T]  = acc + bias as MAED_EPI_GELU ; out[T] = k(r, c) * gelu_erf(out2)            */
+    MAED_EPI_MUL_DGELU_DROP = 10  /* out[T]   = acc * k(r, c) * gelu_erf'(aux[T])                                         */
 } maed_epilogue;
 
 /* kernel implementation selector for ops that have both */
@@ -281,6 +285,32 @@ int maed_dropout_dev(const float* x, float* y, int64_t n, float p, const maed_tr
 /* backward of the GEMM's TANH epilogue (pre_logits, vision_transformer.py:350-353): dx[T] = dy[f32] * (1 - y[T]^2) */
 int maed_tanh_bwd(const float* dy, const void* y, void* dx, int64_t n, int dtype, void* stream);
 
+/* ---- dropout / stochastic depth of the STE blocks (vision_transformer.py:106-112,176-177,259-260; ops/drop.py) ------------------------------------------
+ * MASK DEFINITION (the tests restate it in numpy; all arithmetic mod 2^64):
+ *     keep(seed, idx)  = ((splitmix64_finaliser(seed + (idx + 1) * GOLD) >> 40) >= floor(p * 2^24)),   GOLD = 0x9E3779B97F4A7C15  (maed_dropout's hash)
+ *     block_seed       = `seed`, or with a device record: state->seed + call_id * GOLD                  (as maed_dropout_dev)
+ *     site_seed(s)     = block_seed + s * 0xD1B54A32D192ED03,  s = 1 .. 5:
+ *                        1 Attention.proj_drop, 2 drop_path of the attention branch, 3 Mlp.drop on the hidden activation, 4 Mlp.drop on the output, 5 drop_path of the MLP branch
+ *     element sites 1, 3, 4: idx = r * N + c in the logical (rows, N) tensor;  k(r, c) = keep ? 1 / (1 - drop) : 0
+ *     frame sites 2, 5      : idx = f = r / group_rows (the reference's "sample" is the frame);  g(f) = keep ? 1 / (1 - drop_path) : 0
+ * A rate of 0 (or site 0) means no mask and no hashing at that site.  Nothing is stored: a backward passes the forward's arguments and draws the same masks.
+ * As for maed_dropout the contract with the reference is the distribution, not torch's Philox stream. */
+typedef struct {
+    float drop, drop_path;          /* rates of the element mask / the frame mask, 0 <= rate < 1 */
+    int site_drop, site_path;       /* which site each mask belongs to (0 = none) */
+    uint64_t seed;                  /* block seed (state == NULL) */
+    const maed_train_state* state;  /* device record: the block seed is state->seed + call_id * GOLD, read when the kernel runs (a captured step replays with fresh masks) */
+    uint64_t call_id;
+    int64_t group_rows;             /* rows per frame (frame mask) */
+} maed_drop_args;
+/* maed_gemm_nt with the epilogues MAED_EPI_RESID_DROP_F32 / MAED_EPI_GELU_DROP / MAED_EPI_MUL_DGELU_DROP (N is the mask's row length).  bf16: the 128 x 128 LDS-DMA
+ * kernel (or impl MAED_IMPL_MFMA / MAED_IMPL_VALU); fp32: the exact kernel.  No split-K. */
+int maed_gemm_nt_drop(const void* A, int64_t lda, const void* B, int64_t ldb, int64_t M, int64_t N, int64_t K, int dtype, int epilogue,
+                      const float* bias, void* out, int64_t ldo, void* out2, const void* aux, int64_t ldaux, int impl, const maed_drop_args* drop, void* stream);
+/* out[T](rows, N) = g(r / group_rows) * k(r, c) * in[f32](rows, N), both contiguous: the masked, cast copy of a residual gradient; with T = f32 the stand-alone
+ * DropPath / Dropout of the staged modes.  The same call on the gradient is its backward.  in == out is allowed for T = f32. */
+int maed_drop_scale_cast(const float* in, void* out, int64_t rows, int64_t N, int dtype, const maed_drop_args* drop, void* stream);
+
 /* ---- whole STE Block (vision_transformer.py:244-261 with Attention 'parallel' :146-158,176 and
  *      Mlp :106-112) as ONE host call that enqueues every kernel of the block -------------------- */
 typedef struct {
@@ -335,6 +365,21 @@ int maed_ste_block_infer(const maed_block_dims* d, const maed_block_params* p, c
 int maed_ste_block_bwd(const maed_block_dims* d, const maed_block_params* p, const maed_block_grads* g,
                        const float* x_in, const float* dx_out, float* dx_in, void* saved, void* scratch,
                        const void* dx_out_twin, void* dx_in_twin, void* stream);
+/* The block in training mode with dropout (rate `drop`: sites 1, 3, 4) and stochastic depth (rate `drop_path`: sites 2, 5) -- see "MASK DEFINITION" above:
+ *     x_mid = x_in  + g2[f] k1[r,c] (proj(mix) + b)          h = k3[r,j] gelu(fc1(ln2(x_mid)) + b)          x_out = x_mid + g5[f] k4[r,c] (fc2(h) + b)
+ * The masks ride in the epilogues of the proj / fc1 / fc2 GEMMs (no extra pass in the forward); `saved` keeps its layout (its hidden activation is the dropped
+ * one) and holds no mask.  The backward takes the same `reg` and masks the two branch gradients with one maed_drop_scale_cast each; the residual paths stay
+ * unmasked.  Same buffers and sizes as maed_ste_block_fwd / _bwd; dx_out_twin is ignored (the branch needs the MASKED copy). */
+typedef struct {
+    float drop, drop_path;
+    uint64_t seed;                  /* block seed (state == NULL) */
+    const maed_train_state* state;  /* or the device record + call_id */
+    uint64_t call_id;
+} maed_block_reg;
+int maed_ste_block_fwd_reg(const maed_block_dims* d, const maed_block_params* p, const float* x_in, float* x_out, void* saved, const maed_block_reg* reg,
+                           void* stream);
+int maed_ste_block_bwd_reg(const maed_block_dims* d, const maed_block_params* p, const maed_block_grads* g, const float* x_in, const float* dx_out, float* dx_in,
+                           void* saved, void* scratch, void* dx_in_twin, const maed_block_reg* reg, void* stream);
 
 /* stream ordering helper for hosts that put single launches on a second stream of their own: everything enqueued on from_stream so far happens before whatever
  * is enqueued on to_stream from now on (one event record + one stream wait; the events come from a ring the library owns). */

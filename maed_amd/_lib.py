@@ -14,6 +14,8 @@ LIB_PATH = os.environ.get("MAED_HIP_LIB") or os.path.join(HERE, "libmaed_hip.so"
 F32, BF16 = 0, 1
 F32X3, F32X6, F32X1 = 2, 3, 4     # (F32X1: one bf16 plane -- backward products of the mixed mode) fp32 storage with an explicit matrix-product engine (split-bf16, 3 / 6 MFMAs per product): matrix-product entry points only
 EPI_STORE, EPI_GELU, EPI_RESID_F32, EPI_MUL_DGELU, EPI_ATOMIC_F32, EPI_STORE_F32, EPI_TANH, EPI_ADD = range(8)
+EPI_RESID_DROP_F32, EPI_GELU_DROP, EPI_MUL_DGELU_DROP = 8, 9, 10     # maed_gemm_nt_drop only: the masked epilogues of a regularised STE block
+DROP_GOLD, DROP_SITE = 0x9E3779B97F4A7C15, 0xD1B54A32D192ED03        # include/maed_hip.h "MASK DEFINITION"
 IMPL_AUTO, IMPL_VALU, IMPL_MFMA = 0, 1, 2
 IMPL_MFMA_256 = 6       # gemm_nt only: 256x256 pipelined tiles
 IMPL_MFMA_LONG = 5      # attention only: K/V-tiled long-sequence kernels
@@ -46,6 +48,17 @@ class BlockParams(C.Structure):
 
 class BlockGrads(C.Structure):
     _fields_ = [(n, vp) for n in _GRAD_FIELDS]
+
+
+class DropArgs(C.Structure):
+    """maed_drop_args (include/maed_hip.h): the element mask / frame mask of one site pair"""
+    _fields_ = [("drop", f32), ("drop_path", f32), ("site_drop", i32), ("site_path", i32), ("seed", C.c_uint64), ("state", vp), ("call_id", C.c_uint64),
+                ("group_rows", i64)]
+
+
+class BlockReg(C.Structure):
+    """maed_block_reg (include/maed_hip.h): rates and block seed of a regularised fused block"""
+    _fields_ = [("drop", f32), ("drop_path", f32), ("seed", C.c_uint64), ("state", vp), ("call_id", C.c_uint64)]
 
 
 class SmplParams(C.Structure):
@@ -106,6 +119,10 @@ SIGNATURES = {
     "maed_dropout": (i32, [vp, vp, i64, f32, C.c_uint64, vp]),
     "maed_dropout_dev": (i32, [vp, vp, i64, f32, vp, C.c_uint64, vp]),
     "maed_tanh_bwd": (i32, [vp, vp, vp, i64, i32, vp]),
+    "maed_gemm_nt_drop": (i32, [vp, i64, vp, i64, i64, i64, i64, i32, i32, vp, vp, i64, vp, vp, i64, i32, C.POINTER(DropArgs), vp]),
+    "maed_drop_scale_cast": (i32, [vp, vp, i64, i64, i32, C.POINTER(DropArgs), vp]),
+    "maed_ste_block_fwd_reg": (i32, [C.POINTER(BlockDims), C.POINTER(BlockParams), vp, vp, vp, C.POINTER(BlockReg), vp]),
+    "maed_ste_block_bwd_reg": (i32, [C.POINTER(BlockDims), C.POINTER(BlockParams), C.POINTER(BlockGrads), vp, vp, vp, vp, vp, vp, C.POINTER(BlockReg), vp]),
     "maed_stream_fence": (i32, [vp, vp]),
     "maed_prof_enable": (i32, [i32]),
     "maed_prof_ntags": (i32, []),

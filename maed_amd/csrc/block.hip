@@ -300,7 +300,25 @@ static FwdBufs fwd_bufs(char* act_base, const SavedLayout& A, char* f32_base, co
 
 int maed_gemm_nt_twin(const void* A, int64_t lda, const void* B, int64_t ldb, int64_t M, int64_t N, int64_t K, int dtype, int epilogue, const float* bias, void* out,
                       int64_t ldo, void* out2, const void* aux, int64_t ldaux, int splitk, int impl, void* stream, void* twin, bool out2_bf16, void* lo);      // gemm.hip
-static int block_fwd_bufs(const maed_block_dims* d, const maed_block_params* p, const float* x_in, float* x_out, const FwdBufs& B, bool for_backward, void* stream) {
+// the site pairs of a regularised block (include/maed_hip.h "MASK DEFINITION"): element site + frame site of one masked tensor, `group_rows` rows per frame
+static maed_drop_args reg_sites(const maed_block_reg& r, int site_drop, int site_path, int64_t group_rows) {
+    maed_drop_args a{};
+    a.drop = site_drop ? r.drop : 0.f; a.drop_path = site_path ? r.drop_path : 0.f;
+    a.site_drop = site_drop; a.site_path = site_path;
+    a.seed = r.seed; a.state = r.state; a.call_id = r.call_id; a.group_rows = group_rows;
+    return a;
+}
+static int check_reg(const maed_block_reg* reg, const char* who) {
+    MAED_CHECK_ARG(reg, MAED_ERR_ARG, "%s: null reg", who);
+    MAED_CHECK_ARG(reg->drop >= 0.f && reg->drop < 1.f && reg->drop_path >= 0.f && reg->drop_path < 1.f, MAED_ERR_ARG, "%s: need 0 <= rate < 1 (drop=%f drop_path=%f)", who,
+                   (double)reg->drop, (double)reg->drop_path);
+    return MAED_OK;
+}
+
+// reg != nullptr (maed_ste_block_fwd_reg): the proj and fc2 GEMMs on MAED_EPI_RESID_DROP_F32 (sites 1 + 2, 4 + 5), fc1 on MAED_EPI_GELU_DROP (site 3) -- the saved hidden
+// activation is then the dropped one, which is what the fc2 weight gradient needs; no mask is stored and no pass is added
+static int block_fwd_bufs(const maed_block_dims* d, const maed_block_params* p, const float* x_in, float* x_out, const FwdBufs& B, bool for_backward, void* stream,
+                          const maed_block_reg* reg = nullptr) {
     const int64_t M = (int64_t)d->F * d->P;
     const int C = d->C, Hd = d->hidden, dt = d->dtype;
     const int gi = d->impl == MAED_IMPL_VALU ? MAED_IMPL_VALU : MAED_IMPL_AUTO;
@@ -344,6 +362,10 @@ static int block_fwd_bufs(const maed_block_dims* d, const maed_block_params* p, 
         MAED_PROPAGATE(maed_gemm_nt(B.means, 2 * C, p->w_ts, 2 * C, d->F, 2 * C, 2 * C, dt, MAED_EPI_STORE_F32, p->b_ts, logits, 2 * C, nullptr, nullptr, 0, 1, gi, stream));
         MAED_PROPAGATE(maed_st_mix_fwd(B.xs, B.xt, logits, B.mix, d->F, d->P, C, dt, stream));
     }
+    if (reg) {
+        const maed_drop_args a12 = reg_sites(*reg, 1, 2, d->P);
+        PROF(PROF_GEMM_PROJ, maed_gemm_nt_drop(B.mix, C, p->w_proj, C, M, C, C, dt, MAED_EPI_RESID_DROP_F32, p->b_proj, B.xmid, C, nullptr, x_in, C, gi, &a12, stream));
+    } else
     PROF(PROF_GEMM_PROJ, maed_gemm_nt(B.mix, C, p->w_proj, C, M, C, C, dt, MAED_EPI_RESID_F32, p->b_proj, B.xmid, C, nullptr, x_in, C, 1, gi, stream));
     if (B.ln2_lo) MAED_PROPAGATE(maed_layernorm_fwd_ws((const float*)(B.xmid), C, p->ln2_g, p->ln2_b, B.ln2_hi, MAED_BF16, (float*)(B.mean2), (float*)(B.rstd2), M, C, d->eps,
                                                        nullptr, 0, stream, B.ln2_lo));
@@ -368,6 +390,15 @@ static int block_fwd_bufs(const maed_block_dims* d, const maed_block_params* p, 
         e2.bias = p->b_fc2; e2.out = x_out; e2.ldo = C; e2.aux = B.xmid; e2.ldaux = C;
         PROF(PROF_GEMM_FC2, maed_gemm_nt_x3p_launch(MAED_EPI_RESID_F32, B.planes_variant, B.tw_hact, B.hact_lo, Hd, B.wfc2_hi, B.wfc2_lo, Hd, M, C, Hd, e2, (hipStream_t)stream));
         MAED_CHECK_LAUNCH("ste_block_fwd_twin: fc2 on planes");
+        return MAED_OK;
+    }
+    if (reg) {
+        const maed_drop_args a3 = reg_sites(*reg, 3, 0, d->P), a45 = reg_sites(*reg, 4, 5, d->P);
+        if (reg->drop > 0.f)
+            PROF(PROF_GEMM_FC1, maed_gemm_nt_drop(B.ln2, C, p->w_fc1, C, M, Hd, C, dt, MAED_EPI_GELU_DROP, p->b_fc1, B.hact, Hd, for_backward ? B.hpre : nullptr, nullptr, 0, gi, &a3, stream));
+        else        // stochastic depth alone: fc1 is today's product
+            PROF(PROF_GEMM_FC1, maed_gemm_nt(B.ln2, C, p->w_fc1, C, M, Hd, C, dt, MAED_EPI_GELU, p->b_fc1, B.hact, Hd, for_backward ? B.hpre : nullptr, nullptr, 0, 1, gi, stream));
+        PROF(PROF_GEMM_FC2, maed_gemm_nt_drop(B.hact, Hd, p->w_fc2, Hd, M, C, Hd, dt, MAED_EPI_RESID_DROP_F32, p->b_fc2, x_out, C, nullptr, B.xmid, C, gi, &a45, stream));
         return MAED_OK;
     }
     PROF(PROF_GEMM_FC1, maed_gemm_nt_twin(B.ln2, C, p->w_fc1, C, M, Hd, C, dt, MAED_EPI_GELU, p->b_fc1, B.hact, Hd, for_backward ? B.hpre : nullptr /* only GELU' reads it */, nullptr, 0, 1, gi,
@@ -459,14 +490,27 @@ extern "C" int maed_ste_block_fwd_twin(const maed_block_dims* d, const maed_bloc
 extern "C" int maed_ste_block_fwd(const maed_block_dims* d, const maed_block_params* p, const float* x_in, float* x_out, void* saved, void* stream) {
     return block_fwd(d, p, x_in, x_out, saved, true, stream);
 }
+extern "C" int maed_ste_block_fwd_reg(const maed_block_dims* d, const maed_block_params* p, const float* x_in, float* x_out, void* saved, const maed_block_reg* reg,
+                                      void* stream) {
+    MAED_PROPAGATE(check_dims(d, "ste_block_fwd_reg"));
+    MAED_PROPAGATE(check_reg(reg, "ste_block_fwd_reg"));
+    MAED_CHECK_ARG(p && x_in && x_out && saved, MAED_ERR_ARG, "ste_block_fwd_reg: null pointer");
+    MAED_CHECK_ARG(is_aligned(saved, 256), MAED_ERR_ALIGN, "ste_block_fwd_reg: saved buffer must be 256-B aligned");
+    const SavedLayout L = saved_layout(*d);
+    return block_fwd_bufs(d, p, x_in, x_out, fwd_bufs((char*)saved, L, (char*)saved, L), true, stream, reg);
+}
 // the same forward when no backward will follow (inference): what only the backward reads is not written -- fc1's pre-activation, 103 MB per block at cfg3
 extern "C" int maed_ste_block_infer(const maed_block_dims* d, const maed_block_params* p, const float* x_in, float* x_out, void* work, void* stream) {
     return block_fwd(d, p, x_in, x_out, work, false, stream);
 }
 
-extern "C" int maed_ste_block_bwd(const maed_block_dims* d, const maed_block_params* p, const maed_block_grads* g,
-                                  const float* x_in, const float* dx_out, float* dx_in, void* saved, void* scratch,
-                                  const void* dx_out_twin, void* dx_in_twin, void* stream) {
+// reg != nullptr (maed_ste_block_bwd_reg): the two branch gradients are MASKED copies in the compute dtype, one maed_drop_scale_cast each -- g5 k4 dx_out (sites 4 + 5)
+// in the dyc slot feeds the fc2 weight / bias / input gradients (the input gradient on MAED_EPI_MUL_DGELU_DROP: site 3), g2 k1 dx_mid (sites 1 + 2) in the dyt slot
+// (MFMA path; dyc again in the exact path, where the transposed copy is made FROM the masked one) feeds proj's; they take the places of the handed-along twin of dx_out
+// and of the twin LN2's backward writes.  The residual paths (dres_in of the two LayerNorm backwards) stay unmasked.
+static int block_bwd(const maed_block_dims* d, const maed_block_params* p, const maed_block_grads* g,
+                     const float* x_in, const float* dx_out, float* dx_in, void* saved, void* scratch,
+                     const void* dx_out_twin, void* dx_in_twin, void* stream, const maed_block_reg* reg) {
     MAED_PROPAGATE(check_dims(d, "ste_block_bwd"));
     MAED_CHECK_ARG(p && g && x_in && dx_out && dx_in && saved && scratch, MAED_ERR_ARG, "ste_block_bwd: null pointer");
     MAED_CHECK_ARG(p->wt_qkv && p->wt_ts && p->wt_proj && p->wt_fc1 && p->wt_fc2, MAED_ERR_ARG, "ste_block_bwd: transposed weights missing");
@@ -485,17 +529,23 @@ extern "C" int maed_ste_block_bwd(const maed_block_dims* d, const maed_block_par
     const float scale = 1.0f / sqrtf((float)(d->C / d->H));
     const float* logits = (const float*)(sv + L.logits);
     float* dxmid = (float*)(sc + S.dxmid);
+    maed_drop_args a12{}, a3{}, a45{};
+    if (reg) { a12 = reg_sites(*reg, 1, 2, d->P); a3 = reg_sites(*reg, 3, 0, d->P); a45 = reg_sites(*reg, 4, 5, d->P); }
 
     // (f32: the split TN kernel needs N, K and the row strides -- C, 2C, 3C, hidden -- to be multiples of 4; C = D H (D a multiple of 32) always is, a hidden width that is not falls
     //  through to the exact transposed-copy path below, never less accurate than asked for, as maed_gemm_nt does)
     if (d->impl != MAED_IMPL_VALU && (dt == MAED_BF16 || (maed_x3_planes() && d->hidden % 4 == 0))) {
         // ---- bf16, and f32 in the split-bf16 matmul mode: weight gradients straight from the row-major operands (maed_gemm_tn_wgrad), no transposed copies ----
         const void* dyc = dt == MAED_F32 ? (const void*)dx_out : dx_out_twin;   // dx_out in the compute dtype
+        if (reg) {                                                       // ... masked: g5 k4 dx_out
+            MAED_PROPAGATE(maed_drop_scale_cast(dx_out, sc + S.dyc, M, C, dt, &a45, stream));
+            dyc = sc + S.dyc;
+        } else
         if (!dyc) {                                                      // first block of the backward: cast once
             MAED_PROPAGATE(maed_transpose_cast(dx_out, MAED_F32, C, M, C, nullptr, 0, sc + S.dyc, C, nullptr, dt, stream));
             dyc = sc + S.dyc;
         }
-        void* dxmid_tw = dt == MAED_F32 ? (void*)dxmid : (void*)(sc + S.dyt);   // compute-dtype twin of dx_mid (f32: dx_mid itself; bf16: the old transpose slot)
+        void* dxmid_tw = (dt == MAED_F32 && !reg) ? (void*)dxmid : (void*)(sc + S.dyt);   // compute-dtype twin of dx_mid (f32: dx_mid itself; bf16, and the masked copy: the old transpose slot)
         SideStream* ss = side_stream();
         hipStream_t main_s = (hipStream_t)stream;
         void* wst = ss ? (void*)ss->s : stream;                          // where the weight-gradient GEMMs go
@@ -510,6 +560,9 @@ extern "C" int maed_ste_block_bwd(const maed_block_dims* d, const maed_block_par
         // caller's stream waits for it before the attention backward -- long before the closing LayerNorm.  Keep that wait if the order below is ever changed.
         TO_SIDE();
         WGRAD(maed_gemm_tn_wgrad(dyc, C, sv + L.hact, Hd, M, C, Hd, g->w_fc2, Hd, g->b_fc2, dmm, wst));
+        if (reg && reg->drop > 0.f)
+            PROF(PROF_GEMM_DGRAD, maed_gemm_nt_drop(dyc, C, p->wt_fc2, C, M, Hd, C, dt, MAED_EPI_MUL_DGELU_DROP, nullptr, sc + S.bigA, Hd, nullptr, sv + L.hpre, Hd, gi, &a3, stream));
+        else
         PROF(PROF_GEMM_DGRAD, maed_gemm_nt(dyc, C, p->wt_fc2, C, M, Hd, C, dmm, MAED_EPI_MUL_DGELU, nullptr, sc + S.bigA, Hd, nullptr, sv + L.hpre, Hd, 1, gi, stream));
         TO_SIDE();
         WGRAD(maed_gemm_tn_wgrad(sc + S.bigA, Hd, sv + L.ln2, C, M, Hd, C, g->w_fc1, C, g->b_fc1, dmm, wst));
@@ -528,8 +581,9 @@ extern "C" int maed_ste_block_bwd(const maed_block_dims* d, const maed_block_par
         const bool ln_side = ss != nullptr && ln_part != nullptr && maed_opt(MAED_OPT_ST_FUSED) == 4;
         const bool piggy = st_fused(*d) && maed_opt(MAED_OPT_ST_FUSED) != 2 && (int64_t)d->F * 16 <= 256 * ((M + 31) / 32);
         MAED_PROPAGATE(maed_layernorm_bwd_ws(sc + S.act, dt, (const float*)(sv + L.xmid), C, p->ln2_g, (const float*)(sv + L.mean2), (const float*)(sv + L.rstd2),
-                                             dx_out, dxmid, dt == MAED_F32 ? nullptr : dxmid_tw, g->ln2_g, g->ln2_b, M, C, ln_part, stream, !ln_side,
+                                             dx_out, dxmid, (dt == MAED_F32 || reg) ? nullptr : dxmid_tw, g->ln2_g, g->ln2_b, M, C, ln_part, stream, !ln_side,
                                              piggy ? (uint32_t*)(sv + L.st_sync) : nullptr, piggy ? d->F * 16 : 0));      // (+ clears the counters st_fused_bwd polls)
+        if (reg) MAED_PROPAGATE(maed_drop_scale_cast(dxmid, dxmid_tw, M, C, dt, &a12, stream));                           // g2 k1 dx_mid
         if (ln_side) { TO_SIDE(); MAED_PROPAGATE(maed_layernorm_affine_finish(ln_part, M, C, g->ln2_g, g->ln2_b, wst)); }
         // attention: x_mid = x_in + proj(mix(x_s, x_t))
         TO_SIDE();
@@ -565,9 +619,16 @@ extern "C" int maed_ste_block_bwd(const maed_block_dims* d, const maed_block_par
     }
     // ---- f32 parity mode (and impl = VALU): NT GEMMs on transposed copies ---------------------------------------
     // ---- MLP: x_out = x_mid + fc2(gelu(fc1(ln2(x_mid)))) ------------------------------------------------
+    if (reg) {      // the mask goes before the transpose: masked compute-dtype copy, transposed (and column-summed) from it
+        MAED_PROPAGATE(maed_drop_scale_cast(dx_out, sc + S.dyc, M, C, dt, &a45, stream));
+        MAED_PROPAGATE(maed_transpose_cast(sc + S.dyc, dt, C, M, C, sc + S.dyt, Mp, nullptr, 0, g->b_fc2, dt, stream));
+    } else
     MAED_PROPAGATE(maed_transpose_cast(dx_out, MAED_F32, C, M, C, sc + S.dyt, Mp, sc + S.dyc, C, g->b_fc2, dt, stream));
     MAED_PROPAGATE(maed_transpose_cast(sv + L.hact, dt, Hd, M, Hd, sc + S.bigT, Mp, nullptr, 0, nullptr, dt, stream));
     PROF(PROF_GEMM_WGRAD, wgrad(sc + S.dyt, sc + S.bigT, C, Hd, Mp, g->w_fc2, *d, stream));
+    if (reg && reg->drop > 0.f)
+        MAED_PROPAGATE(maed_gemm_nt_drop(sc + S.dyc, C, p->wt_fc2, C, M, Hd, C, dt, MAED_EPI_MUL_DGELU_DROP, nullptr, sc + S.bigA, Hd, nullptr, sv + L.hpre, Hd, gi, &a3, stream));
+    else
     MAED_PROPAGATE(maed_gemm_nt(sc + S.dyc, C, p->wt_fc2, C, M, Hd, C, dt, MAED_EPI_MUL_DGELU, nullptr, sc + S.bigA, Hd, nullptr, sv + L.hpre, Hd, 1, gi, stream));
     MAED_PROPAGATE(maed_transpose_cast(sc + S.bigA, dt, Hd, M, Hd, sc + S.bigT, Mp, nullptr, 0, g->b_fc1, dt, stream));
     MAED_PROPAGATE(maed_transpose_cast(sv + L.ln2, dt, C, M, C, sc + S.xT, Mp, nullptr, 0, nullptr, dt, stream));
@@ -576,6 +637,10 @@ extern "C" int maed_ste_block_bwd(const maed_block_dims* d, const maed_block_par
     MAED_PROPAGATE(maed_layernorm_bwd(sc + S.act, dt, (const float*)(sv + L.xmid), C, p->ln2_g, (const float*)(sv + L.mean2), (const float*)(sv + L.rstd2),
                                       dx_out, dxmid, nullptr, g->ln2_g, g->ln2_b, M, C, stream));
     // ---- attention: x_mid = x_in + proj(mix(x_s, x_t)) ---------------------------------------------------
+    if (reg) {
+        MAED_PROPAGATE(maed_drop_scale_cast(dxmid, sc + S.dyc, M, C, dt, &a12, stream));
+        MAED_PROPAGATE(maed_transpose_cast(sc + S.dyc, dt, C, M, C, sc + S.dyt, Mp, nullptr, 0, g->b_proj, dt, stream));
+    } else
     MAED_PROPAGATE(maed_transpose_cast(dxmid, MAED_F32, C, M, C, sc + S.dyt, Mp, sc + S.dyc, C, g->b_proj, dt, stream));
     MAED_PROPAGATE(maed_transpose_cast(sv + L.mix, dt, C, M, C, sc + S.xT, Mp, nullptr, 0, nullptr, dt, stream));
     PROF(PROF_GEMM_WGRAD, wgrad(sc + S.dyt, sc + S.xT, C, C, Mp, g->w_proj, *d, stream));
@@ -596,6 +661,17 @@ extern "C" int maed_ste_block_bwd(const maed_block_dims* d, const maed_block_par
     MAED_PROPAGATE(maed_layernorm_bwd(sc + S.act, dt, x_in, C, p->ln1_g, (const float*)(sv + L.mean1), (const float*)(sv + L.rstd1), dxmid, dx_in, dx_in_twin,
                                       g->ln1_g, g->ln1_b, M, C, stream));
     return MAED_OK;
+}
+
+extern "C" int maed_ste_block_bwd(const maed_block_dims* d, const maed_block_params* p, const maed_block_grads* g,
+                                  const float* x_in, const float* dx_out, float* dx_in, void* saved, void* scratch,
+                                  const void* dx_out_twin, void* dx_in_twin, void* stream) {
+    return block_bwd(d, p, g, x_in, dx_out, dx_in, saved, scratch, dx_out_twin, dx_in_twin, stream, nullptr);
+}
+extern "C" int maed_ste_block_bwd_reg(const maed_block_dims* d, const maed_block_params* p, const maed_block_grads* g, const float* x_in, const float* dx_out, float* dx_in,
+                                      void* saved, void* scratch, void* dx_in_twin, const maed_block_reg* reg, void* stream) {
+    MAED_PROPAGATE(check_reg(reg, "ste_block_bwd_reg"));
+    return block_bwd(d, p, g, x_in, dx_out, dx_in, saved, scratch, nullptr, dx_in_twin, stream, reg);
 }
 
 // ---- error plumbing / version ------------------------------------------------------------------------

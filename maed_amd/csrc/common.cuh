@@ -283,6 +283,64 @@ template <typename T> __device__ __forceinline__ float round_to(float x);
 template <> __device__ __forceinline__ float round_to<float>(float x) { return x; }
 template <> __device__ __forceinline__ float round_to<struct bf16>(float x) { return bf2f(f2bf(x)); }
 
+// ---- counter-based keep mask (nn.Dropout / DropPath; include/maed_hip.h "mask definition") -----------------------------------------------------------
+// keep(seed, idx): splitmix64 finaliser of seed + (idx + 1) * GOLD, top 24 bits against floor(p * 2^24).  Nothing is stored: a backward draws the forward's mask
+// again from the same (seed, idx).
+#define MAED_DROP_GOLD 0x9E3779B97F4A7C15ull
+#define MAED_DROP_SITE 0xD1B54A32D192ED03ull
+__device__ __forceinline__ bool dropout_keep(uint64_t seed, uint64_t idx, uint32_t thresh24) {
+    uint64_t z = seed + (idx + 1) * MAED_DROP_GOLD;                        // splitmix64 finaliser
+    z = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9ull;
+    z = (z ^ (z >> 27)) * 0x94D049BB133111EBull;
+    z ^= z >> 31;
+    return (uint32_t)(z >> 40) >= thresh24;                                // top 24 bits uniform in [0, 2^24)
+}
+static inline uint32_t dropout_thresh24(float p) { return (uint32_t)((double)p * 16777216.0); }
+
+// The two masks of one site pair of a regularised STE block, as a kernel argument (host side: maed_drop_args -> make_epi_drop, csrc/gemm.hip):
+//   element mask k(r, c) = keep(seed_k, r * N + c) ? scale_k : 0     (thresh_k = 0: no element mask, k = 1)
+//   frame mask   g(r)    = keep(seed_g, r / group_rows) ? scale_g : 0 (thresh_g = 0: no frame mask, g = 1)
+// seed_k / seed_g = block seed + site * MAED_DROP_SITE; with a device record the block seed is state->seed + `seed` (= call_id * GOLD), read when the kernel runs.
+struct EpiDrop {
+    const maed_train_state* state = nullptr;
+    uint64_t seed = 0;
+    uint32_t thresh_k = 0, thresh_g = 0;
+    float scale_k = 1.f, scale_g = 1.f;
+    int32_t site_k = 0, site_g = 0;
+    int64_t group_rows = 1, N = 0;
+};
+// host: the public description of a site pair -> the kernel argument (N: row length of the logical tensor the element mask indexes)
+static inline int maed_make_epi_drop(const maed_drop_args* a, int64_t N, EpiDrop* out, const char* who) {
+    MAED_CHECK_ARG(a, MAED_ERR_ARG, "%s: null drop arguments", who);
+    MAED_CHECK_ARG(a->drop >= 0.f && a->drop < 1.f && a->drop_path >= 0.f && a->drop_path < 1.f, MAED_ERR_ARG, "%s: need 0 <= rate < 1 (drop=%f drop_path=%f)", who,
+                   (double)a->drop, (double)a->drop_path);
+    MAED_CHECK_ARG(a->site_drop >= 0 && a->site_drop <= 5 && a->site_path >= 0 && a->site_path <= 5, MAED_ERR_ARG, "%s: sites are 0 (none) or 1 .. 5", who);
+    MAED_CHECK_ARG(a->group_rows >= 1 || a->site_path == 0 || a->drop_path == 0.f, MAED_ERR_ARG, "%s: the frame mask needs group_rows >= 1", who);
+    MAED_CHECK_ARG(!a->state || is_aligned(a->state, 8), MAED_ERR_ALIGN, "%s: state must be 8-B aligned", who);
+    EpiDrop d;
+    d.state = a->state;
+    d.seed = a->state ? a->call_id * MAED_DROP_GOLD : a->seed;
+    if (a->site_drop && a->drop > 0.f) { d.thresh_k = dropout_thresh24(a->drop); d.scale_k = 1.0f / (1.0f - a->drop); d.site_k = a->site_drop; }
+    if (a->site_path && a->drop_path > 0.f) { d.thresh_g = dropout_thresh24(a->drop_path); d.scale_g = 1.0f / (1.0f - a->drop_path); d.site_g = a->site_path; }
+    d.group_rows = a->group_rows >= 1 ? a->group_rows : 1;
+    d.N = N;
+    *out = d;
+    return MAED_OK;
+}
+struct DropSeeds { uint64_t k, g; };
+__device__ __forceinline__ DropSeeds drop_seeds(const EpiDrop& d) {
+    const uint64_t base = (d.state ? d.state->seed : 0ull) + d.seed;
+    return DropSeeds{base + (uint64_t)d.site_k * MAED_DROP_SITE, base + (uint64_t)d.site_g * MAED_DROP_SITE};
+}
+__device__ __forceinline__ float drop_row_scale(const EpiDrop& d, const DropSeeds& s, int64_t r) {
+    if (d.thresh_g == 0) return 1.f;
+    return dropout_keep(s.g, (uint64_t)(r / d.group_rows), d.thresh_g) ? d.scale_g : 0.f;
+}
+__device__ __forceinline__ float drop_elem_scale(const EpiDrop& d, const DropSeeds& s, int64_t r, int64_t c) {
+    if (d.thresh_k == 0) return 1.f;
+    return dropout_keep(s.k, (uint64_t)(r * d.N + c), d.thresh_k) ? d.scale_k : 0.f;
+}
+
 template <typename T> struct dtype_of;
 template <> struct dtype_of<float> { static constexpr int value = MAED_F32; };
 template <> struct dtype_of<bf16> { static constexpr int value = MAED_BF16; };

@@ -584,13 +584,7 @@ extern "C" int maed_transpose_cast(const void* in, int in_dtype, int64_t ldi, in
 // (The reference draws its mask from torch's Philox stream on whatever device it runs on; no two devices share that stream, so
 // the contract is the distribution: keep probability 1-p, survivors scaled by 1/(1-p).)
 // ---------------------------------------------------------------------------------------------------
-__device__ __forceinline__ bool dropout_keep(uint64_t seed, uint64_t idx, uint32_t thresh24) {
-    uint64_t z = seed + (idx + 1) * 0x9E3779B97F4A7C15ull;                 // splitmix64 finaliser
-    z = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9ull;
-    z = (z ^ (z >> 27)) * 0x94D049BB133111EBull;
-    z ^= z >> 31;
-    return (uint32_t)(z >> 40) >= thresh24;                                // top 24 bits uniform in [0, 2^24)
-}
+// (dropout_keep: csrc/common.cuh -- the GEMM epilogues of a regularised STE block draw the same mask)
 
 // y = keep ? x * scale : 0     (the same kernel is its own backward: dx = keep ? dy * scale : 0)
 __global__ __launch_bounds__(256) void dropout_kernel(const float* __restrict__ x, float* __restrict__ y, int64_t n, uint64_t seed, uint32_t thresh24,
@@ -626,6 +620,48 @@ extern "C" int maed_dropout_dev(const float* x, float* y, int64_t n, float p, co
     const uint32_t thresh = (uint32_t)((double)p * 16777216.0);
     hipLaunchKernelGGL(dropout_dev_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, (hipStream_t)stream, x, y, n, state, call_id, thresh, 1.0f / (1.0f - p));
     MAED_CHECK_LAUNCH("dropout_dev");
+    return MAED_OK;
+}
+
+// out[T](rows, N) = g(r / group_rows) * k(r, c) * in[f32]: the masked (and cast) copy of a residual gradient in the backward of a regularised STE block, and with
+// T = float the DropPath / Dropout of the staged modes (vision_transformer.py:107-111,177,259-260; ops/drop.py).  The masks are those of the GEMM epilogues
+// (common.cuh EpiDrop), so the same call on a gradient is the backward of the masked epilogue.  W = 8: a thread owns 8 consecutive columns of one row (N % 8 == 0).
+template <typename T, int W>
+__global__ __launch_bounds__(256) void drop_scale_cast_kernel(const float* in, T* out, int64_t rows, int64_t N, EpiDrop d) {      // (no __restrict__: T = float may run in place)
+    const int64_t i = ((int64_t)blockIdx.x * 256 + threadIdx.x) * W;
+    if (i >= rows * N) return;
+    const int64_t r = i / N, c0 = i - r * N;
+    const DropSeeds sd = drop_seeds(d);
+    const float g = drop_row_scale(d, sd, r);
+    float v[W];
+    if constexpr (W == 8) ld8(in + i, v); else v[0] = in[i];
+#pragma unroll
+    for (int j = 0; j < W; ++j) v[j] = g == 0.f ? 0.f : (g * drop_elem_scale(d, sd, r, c0 + j)) * v[j];
+    if constexpr (W == 8) st8(out + i, v); else stf(out + i, v[0]);
+}
+
+extern "C" int maed_drop_scale_cast(const float* in, void* out, int64_t rows, int64_t N, int dtype, const maed_drop_args* drop, void* stream) {
+    MAED_CHECK_ARG(in && out, MAED_ERR_ARG, "drop_scale_cast: null pointer");
+    MAED_CHECK_ARG(dtype == MAED_F32 || dtype == MAED_BF16, MAED_ERR_ARG, "drop_scale_cast: bad dtype %d", dtype);
+    MAED_CHECK_ARG(rows >= 0 && N > 0, MAED_ERR_SHAPE, "drop_scale_cast: bad extents rows=%lld N=%lld", (long long)rows, (long long)N);
+    MAED_CHECK_ARG(dtype == MAED_F32 || (const void*)in != out, MAED_ERR_ARG, "drop_scale_cast: in place needs an fp32 output");
+    EpiDrop d;
+    MAED_PROPAGATE(maed_make_epi_drop(drop, N, &d, "drop_scale_cast"));
+    if (rows == 0) return MAED_OK;
+    const int64_t n = rows * N;
+    const bool wide = N % 8 == 0 && is_aligned(in, 16) && is_aligned(out, 16);
+    const int64_t threads = wide ? n / 8 : n;
+    MAED_CHECK_ARG((threads + 255) / 256 < (1ll << 31), MAED_ERR_SHAPE, "drop_scale_cast: tensor too large");
+    const dim3 grid((unsigned)((threads + 255) / 256));
+    hipStream_t s = (hipStream_t)stream;
+    if (dtype == MAED_F32) {
+        if (wide) hipLaunchKernelGGL((drop_scale_cast_kernel<float, 8>), grid, dim3(256), 0, s, in, (float*)out, rows, N, d);
+        else hipLaunchKernelGGL((drop_scale_cast_kernel<float, 1>), grid, dim3(256), 0, s, in, (float*)out, rows, N, d);
+    } else {
+        if (wide) hipLaunchKernelGGL((drop_scale_cast_kernel<bf16, 8>), grid, dim3(256), 0, s, in, (bf16*)out, rows, N, d);
+        else hipLaunchKernelGGL((drop_scale_cast_kernel<bf16, 1>), grid, dim3(256), 0, s, in, (bf16*)out, rows, N, d);
+    }
+    MAED_CHECK_LAUNCH("drop_scale_cast");
     return MAED_OK;
 }
 

@@ -556,6 +556,44 @@ int maed_gemm_nt_twin(const void* A, int64_t lda, const void* B, int64_t ldb, in
     return MAED_OK;
 }
 
+// ---- the masked epilogues of a regularised STE block (MAED_EPI_*_DROP) ---------------------------------------------------------------------------------
+// Routed to three kernel families only, the ones that between them carry the three store forms: the exact kernel (scalar; every fp32 call, impl VALU, operands the
+// MFMA kernels cannot stage), the register-staged MFMA kernel (4-wide; impl MFMA, or operands past the LDS-DMA kernel's 32-bit offsets) and the 128 x 128 LDS-DMA
+// kernel (8-wide, LDS-shuffled: the default in bf16).  The 256 x 256 / persistent / split-bf16 families do not instantiate them.
+template <int EPI>
+static int dispatch_drop(const void* A, int64_t lda, const void* B, int64_t ldb, int64_t M, int64_t N, int64_t K, int dtype, const EpiArgs& e, int impl, hipStream_t s) {
+    if (dtype == MAED_F32) return launch_valu<EPI, float>(A, lda, B, ldb, M, N, K, e, 1, s);
+    const bool fits32 = (uint64_t)M * (uint64_t)lda * 2 < (1ull << 32) && (uint64_t)N * (uint64_t)ldb * 2 < (1ull << 32);
+    const bool mfma_ok = (K % GM_BK == 0) && (lda % 8 == 0) && (ldb % 8 == 0) && is_aligned(A, 16) && is_aligned(B, 16);
+    if (impl == MAED_IMPL_VALU || !mfma_ok) {
+        MAED_CHECK_ARG(impl == MAED_IMPL_VALU || impl == MAED_IMPL_AUTO, MAED_ERR_ALIGN, "gemm_nt_drop(mfma): need K%%64==0 (K=%lld), lda/ldb%%8==0, 16-B aligned A/B", (long long)K);
+        return launch_valu<EPI, bf16>(A, lda, B, ldb, M, N, K, e, 1, s);
+    }
+    if (impl == MAED_IMPL_MFMA || !fits32) return launch_mfma<EPI>(A, lda, B, ldb, M, N, K, e, 1, s);
+    return launch_glds<EPI, 1>(A, lda, B, ldb, M, N, K, e, 1, s);
+}
+
+extern "C" int maed_gemm_nt_drop(const void* A, int64_t lda, const void* B, int64_t ldb, int64_t M, int64_t N, int64_t K, int dtype, int epilogue, const float* bias,
+                                 void* out, int64_t ldo, void* out2, const void* aux, int64_t ldaux, int impl, const maed_drop_args* drop, void* stream) {
+    MAED_CHECK_ARG(A && B && out, MAED_ERR_ARG, "gemm_nt_drop: null pointer");
+    MAED_CHECK_ARG(dtype == MAED_F32 || dtype == MAED_BF16, MAED_ERR_ARG, "gemm_nt_drop: bad dtype %d", dtype);
+    MAED_CHECK_ARG(impl == MAED_IMPL_AUTO || impl == MAED_IMPL_VALU || (dtype == MAED_BF16 && (impl == MAED_IMPL_MFMA || impl == MAED_IMPL_MFMA_GLDS1)), MAED_ERR_UNSUPPORTED,
+                   "gemm_nt_drop: impl %d (the masked epilogues exist on the exact, the register-staged MFMA and the 128 x 128 LDS-DMA kernels)", impl);
+    MAED_CHECK_ARG(M >= 0 && N > 0 && K > 0 && lda >= K && ldb >= K && ldo >= N, MAED_ERR_SHAPE, "gemm_nt_drop: bad extents M=%lld N=%lld K=%lld", (long long)M, (long long)N, (long long)K);
+    MAED_CHECK_ARG(epilogue == MAED_EPI_GELU_DROP || (aux && ldaux >= N), MAED_ERR_ARG, "gemm_nt_drop: the RESID_DROP / MUL_DGELU_DROP epilogues need aux");
+    EpiArgs e{bias, out, ldo, out2, aux, ldaux};
+    MAED_PROPAGATE(maed_make_epi_drop(drop, N, &e.drop, "gemm_nt_drop"));
+    if (M == 0) return MAED_OK;
+    int rc = MAED_OK;
+    if (!epilogue_switch<EPI_SET_DROP>(epilogue, [&](auto epi) { rc = dispatch_drop<decltype(epi)::value>(A, lda, B, ldb, M, N, K, dtype, e, impl, (hipStream_t)stream); })) {
+        maed_set_error("gemm_nt_drop: epilogue %d is not one of MAED_EPI_RESID_DROP_F32 / _GELU_DROP / _MUL_DGELU_DROP", epilogue);
+        return MAED_ERR_ARG;
+    }
+    if (rc != MAED_OK) return rc;
+    MAED_CHECK_LAUNCH("gemm_nt_drop");
+    return MAED_OK;
+}
+
 // The 3x3 convolutions on this file's tile, LDS image and epilogue are part of this translation unit (the library's and the host
 // simulator's source lists name gemm.hip): Conv3x3Dims, the two kernels, maed_conv3x3_fwd and maed_conv3x3_s2_dgrad.
 #include "conv3x3.hip"

@@ -21,7 +21,21 @@ struct EpiArgs {
     // plane storage of the same output (csrc/gemm_x3p.hip; T = float only): `twin` is the hi plane, `lo` = bf16(value - hi) with the twin's leading dimension -- the next
     // split product reads (twin, lo) instead of fp32; `out` may then be NULL (nothing else reads the fp32 form)
     void* lo = nullptr;
+    // masks of a regularised STE block (MAED_EPI_*_DROP only; common.cuh EpiDrop): the element mask k(r, c) and the frame mask g(r / group_rows), drawn in the epilogue
+    EpiDrop drop = {};
 };
+
+// a *_DROP epilogue is its base epilogue with the branch term masked: the address arithmetic, vector forms and alignment rules are the base's
+template <int EPI> struct epi_base { static constexpr int value = EPI == MAED_EPI_RESID_DROP_F32 ? MAED_EPI_RESID_F32 : EPI == MAED_EPI_GELU_DROP ? MAED_EPI_GELU :
+                                                                  EPI == MAED_EPI_MUL_DGELU_DROP ? MAED_EPI_MUL_DGELU : EPI; };
+// W consecutive element masks of row r times the row's frame mask (RESID_DROP: both; GELU_DROP / MUL_DGELU_DROP: the element mask alone)
+template <int EPI, int W>
+__device__ __forceinline__ void epi_drop_scales(const EpiArgs& e, int64_t r, int64_t c0, float (&m)[W]) {
+    const DropSeeds sd = drop_seeds(e.drop);
+    const float g = EPI == MAED_EPI_RESID_DROP_F32 ? drop_row_scale(e.drop, sd, r) : 1.f;
+#pragma unroll
+    for (int j = 0; j < W; ++j) m[j] = g == 0.f ? 0.f : g * drop_elem_scale(e.drop, sd, r, c0 + j);      // (a dropped frame hashes no element)
+}
 
 // the (hi, lo) bf16 planes of eight fp32 values: hi = bf16(v) (round to nearest even), lo = bf16(v - hi) -- gemm_x3.h's split4<2>
 __device__ __forceinline__ void epi_store_planes8(bf16* hi, bf16* lo, const float (&v)[8]) {
@@ -32,8 +46,12 @@ __device__ __forceinline__ void epi_store_planes8(bf16* hi, bf16* lo, const floa
     if (lo) st8_nt(lo, l);
 }
 
-template <int EPI, typename T>
+template <int EPI_, typename T>
 __device__ __forceinline__ void epilogue_store(const EpiArgs& e, int64_t r, int64_t c, float acc) {
+    constexpr int EPI = epi_base<EPI_>::value;
+    constexpr bool DROP = EPI != EPI_;
+    float m[1] = {1.f};
+    if constexpr (DROP) epi_drop_scales<EPI_, 1>(e, r, c, m);
     if constexpr (EPI == MAED_EPI_STORE) {
         const float v = acc + (e.bias ? e.bias[c] : 0.f);
         if (sizeof(T) != 4 || e.out) stf((T*)e.out + r * e.ldo + c, v);
@@ -41,13 +59,15 @@ __device__ __forceinline__ void epilogue_store(const EpiArgs& e, int64_t r, int6
     } else if constexpr (EPI == MAED_EPI_GELU) {
         const float pre = acc + (e.bias ? e.bias[c] : 0.f);
         if (e.out2) { if (sizeof(T) == 4 && e.out2_bf16) stf((bf16*)e.out2 + r * e.ldo + c, pre); else stf((T*)e.out2 + r * e.ldo + c, pre); }   // (out2 = NULL: nobody will ask for GELU', inference)
-        const float a = gelu_fwd<T>(round_to<T>(pre));
+        const float a = DROP ? m[0] * gelu_fwd<T>(round_to<T>(pre)) : gelu_fwd<T>(round_to<T>(pre));
         if (sizeof(T) != 4 || e.out) stf((T*)e.out + r * e.ldo + c, a);  // activation of the STORED (rounded) pre-activation
         if constexpr (sizeof(T) == 4) { if (e.twin) stf((bf16*)e.twin + r * e.ldo + c, a); if (e.lo) stf((bf16*)e.lo + r * e.ldo + c, a - round_to<bf16>(a)); }
     } else if constexpr (EPI == MAED_EPI_RESID_F32) {
-        ((float*)e.out)[r * e.ldo + c] = ((const float*)e.aux)[r * e.ldaux + c] + (acc + (e.bias ? e.bias[c] : 0.f));
+        const float v = acc + (e.bias ? e.bias[c] : 0.f);
+        ((float*)e.out)[r * e.ldo + c] = ((const float*)e.aux)[r * e.ldaux + c] + (DROP ? m[0] * v : v);
     } else if constexpr (EPI == MAED_EPI_MUL_DGELU) {
-        stf((T*)e.out + r * e.ldo + c, acc * gelu_bwd<T>(ldf((const T*)e.aux + r * e.ldaux + c)));
+        const float v = acc * gelu_bwd<T>(ldf((const T*)e.aux + r * e.ldaux + c));
+        stf((T*)e.out + r * e.ldo + c, DROP ? m[0] * v : v);
     } else if constexpr (EPI == MAED_EPI_ATOMIC_F32) {
         atomicAdd((float*)e.out + r * e.ldo + c, acc);
     } else if constexpr (EPI == MAED_EPI_STORE_F32) {
@@ -63,8 +83,9 @@ __device__ __forceinline__ void epilogue_store(const EpiArgs& e, int64_t r, int6
 
 // May a kernel use the W-wide (W = 4, 8) forms below: every row of out / out2 / aux starts a multiple of W elements from a base that is aligned for the
 // widest access of W elements (16 bytes at most: wider ones are split), and so does bias.  out2 counts for GELU only (the ADD mask is read bytewise).
-template <int EPI, typename T, int W>
+template <int EPI_, typename T, int W>
 __device__ __forceinline__ bool epilogue_vec_ok(const EpiArgs& e) {
+    constexpr int EPI = epi_base<EPI_>::value;
     constexpr bool f32_out = sizeof(T) == 4 || EPI == MAED_EPI_RESID_F32 || EPI == MAED_EPI_STORE_F32 || EPI == MAED_EPI_ATOMIC_F32;
     constexpr uintptr_t out_mask = (W * (f32_out ? 4 : 2) < 16 ? W * (f32_out ? 4 : 2) : 16) - 1;
     constexpr uintptr_t aux_mask = (W * (EPI == MAED_EPI_RESID_F32 ? 4 : (int)sizeof(T)) < 16 ? W * (EPI == MAED_EPI_RESID_F32 ? 4 : (int)sizeof(T)) : 16) - 1;
@@ -75,14 +96,18 @@ __device__ __forceinline__ bool epilogue_vec_ok(const EpiArgs& e) {
 
 // four consecutive columns c0..c0+3 of one row (c0 % 4 == 0): 8/16-byte accesses when the row base is aligned.  bf16 storage only (the register-staged
 // MFMA kernel): the twin / plane outputs of the fp32 products are written by the scalar and the 8-wide forms
-template <int EPI, typename T>
+template <int EPI_, typename T>
 __device__ __forceinline__ void epilogue_store4(const EpiArgs& e, int64_t r, int64_t c0, int64_t N, const float (&acc)[4], bool vec_ok) {
     static_assert(sizeof(T) == 2, "epilogue_store4 carries no twin / lo outputs: fp32 storage goes through epilogue_store / epilogue_store8");
+    constexpr int EPI = epi_base<EPI_>::value;
+    constexpr bool DROP = EPI != EPI_;
     if (!(vec_ok && c0 + 4 <= N)) {
 #pragma unroll
-        for (int j = 0; j < 4; ++j) if (c0 + j < N) epilogue_store<EPI, T>(e, r, c0 + j, acc[j]);
+        for (int j = 0; j < 4; ++j) if (c0 + j < N) epilogue_store<EPI_, T>(e, r, c0 + j, acc[j]);
         return;
     }
+    float m[4] = {1.f, 1.f, 1.f, 1.f};
+    if constexpr (DROP) epi_drop_scales<EPI_, 4>(e, r, c0, m);
     float v[4] = {acc[0], acc[1], acc[2], acc[3]};
     if constexpr (EPI == MAED_EPI_ATOMIC_F32) {
 #pragma unroll
@@ -98,14 +123,17 @@ __device__ __forceinline__ void epilogue_store4(const EpiArgs& e, int64_t r, int
         if (e.out2) st4((T*)e.out2 + r * e.ldo + c0, v);
         // activation of the STORED (rounded) pre-activation, as the backward sees it -- rounded in registers, not read back
         float a[4] = {gelu_fwd<T>(round_to<T>(v[0])), gelu_fwd<T>(round_to<T>(v[1])), gelu_fwd<T>(round_to<T>(v[2])), gelu_fwd<T>(round_to<T>(v[3]))};
+        if constexpr (DROP) { a[0] *= m[0]; a[1] *= m[1]; a[2] *= m[2]; a[3] *= m[3]; }
         st4((T*)e.out + r * e.ldo + c0, a);
     } else if constexpr (EPI == MAED_EPI_RESID_F32) {
         float x[4]; ld4((const float*)e.aux + r * e.ldaux + c0, x);
+        if constexpr (DROP) { v[0] *= m[0]; v[1] *= m[1]; v[2] *= m[2]; v[3] *= m[3]; }
         float o[4] = {x[0] + v[0], x[1] + v[1], x[2] + v[2], x[3] + v[3]};
         st4((float*)e.out + r * e.ldo + c0, o);
     } else if constexpr (EPI == MAED_EPI_MUL_DGELU) {
         float x[4]; ld4((const T*)e.aux + r * e.ldaux + c0, x);
         float o[4] = {v[0] * gelu_bwd<T>(x[0]), v[1] * gelu_bwd<T>(x[1]), v[2] * gelu_bwd<T>(x[2]), v[3] * gelu_bwd<T>(x[3])};
+        if constexpr (DROP) { o[0] *= m[0]; o[1] *= m[1]; o[2] *= m[2]; o[3] *= m[3]; }
         st4((T*)e.out + r * e.ldo + c0, o);
     } else if constexpr (EPI == MAED_EPI_STORE_F32) {
         st4((float*)e.out + r * e.ldo + c0, v);
@@ -126,13 +154,17 @@ __device__ __forceinline__ void epilogue_store4(const EpiArgs& e, int64_t r, int
 
 // eight consecutive columns c0..c0+7 of one row (c0 % 8 == 0): 16/32-byte accesses (the LDS-shuffled epilogue of the
 // direct-to-LDS kernels: 8 lanes cover a 64-column row segment = one or two full cache lines per row)
-template <int EPI, typename T>
+template <int EPI_, typename T>
 __device__ __forceinline__ void epilogue_store8(const EpiArgs& e, int64_t r, int64_t c0, int64_t N, const float (&acc)[8], bool vec_ok) {
+    constexpr int EPI = epi_base<EPI_>::value;
+    constexpr bool DROP = EPI != EPI_;
     if (!(vec_ok && c0 + 8 <= N)) {
 #pragma unroll
-        for (int j = 0; j < 8; ++j) if (c0 + j < N) epilogue_store<EPI, T>(e, r, c0 + j, acc[j]);
+        for (int j = 0; j < 8; ++j) if (c0 + j < N) epilogue_store<EPI_, T>(e, r, c0 + j, acc[j]);
         return;
     }
+    float m[8] = {1.f, 1.f, 1.f, 1.f, 1.f, 1.f, 1.f, 1.f};
+    if constexpr (DROP) epi_drop_scales<EPI_, 8>(e, r, c0, m);
     float v[8];
 #pragma unroll
     for (int j = 0; j < 8; ++j) v[j] = acc[j];
@@ -148,18 +180,18 @@ __device__ __forceinline__ void epilogue_store8(const EpiArgs& e, int64_t r, int
         if (e.out2) { if (sizeof(T) == 4 && e.out2_bf16) st8_nt((bf16*)e.out2 + r * e.ldo + c0, v); else st8((T*)e.out2 + r * e.ldo + c0, v); }
         float a[8];
 #pragma unroll
-        for (int j = 0; j < 8; ++j) a[j] = gelu_fwd<T>(round_to<T>(v[j]));   // activation of the STORED (rounded) pre-activation
+        for (int j = 0; j < 8; ++j) a[j] = DROP ? m[j] * gelu_fwd<T>(round_to<T>(v[j])) : gelu_fwd<T>(round_to<T>(v[j]));   // activation of the STORED (rounded) pre-activation
         if (sizeof(T) != 4 || e.out) st8((T*)e.out + r * e.ldo + c0, a);
         if constexpr (sizeof(T) == 4) { if (e.twin) epi_store_planes8((bf16*)e.twin + r * e.ldo + c0, e.lo ? (bf16*)e.lo + r * e.ldo + c0 : nullptr, a); }
     } else if constexpr (EPI == MAED_EPI_RESID_F32) {
         float x[8]; ld8((const float*)e.aux + r * e.ldaux + c0, x);
 #pragma unroll
-        for (int j = 0; j < 8; ++j) x[j] += v[j];
+        for (int j = 0; j < 8; ++j) x[j] += DROP ? m[j] * v[j] : v[j];
         st8((float*)e.out + r * e.ldo + c0, x);
     } else if constexpr (EPI == MAED_EPI_MUL_DGELU) {
         float x[8]; ld8((const T*)e.aux + r * e.ldaux + c0, x);
 #pragma unroll
-        for (int j = 0; j < 8; ++j) x[j] = v[j] * gelu_bwd<T>(x[j]);
+        for (int j = 0; j < 8; ++j) x[j] = DROP ? m[j] * (v[j] * gelu_bwd<T>(x[j])) : v[j] * gelu_bwd<T>(x[j]);
         st8((T*)e.out + r * e.ldo + c0, x);
     } else if constexpr (EPI == MAED_EPI_STORE_F32) {
         st8((float*)e.out + r * e.ldo + c0, v);
@@ -314,10 +346,12 @@ __device__ __forceinline__ void epilogue_shuffled(const f32x16_t& accA, const f3
 constexpr unsigned EPI_SET_STORES = EPI_BIT(MAED_EPI_STORE) | EPI_BIT(MAED_EPI_GELU) | EPI_BIT(MAED_EPI_RESID_F32) | EPI_BIT(MAED_EPI_MUL_DGELU) |
                                     EPI_BIT(MAED_EPI_STORE_F32) | EPI_BIT(MAED_EPI_TANH) | EPI_BIT(MAED_EPI_ADD);      // everything but the fp32 atomics
 constexpr unsigned EPI_SET_ALL = EPI_SET_STORES | EPI_BIT(MAED_EPI_ATOMIC_F32);
+// the masked epilogues of a regularised STE block: instantiated by maed_gemm_nt_drop's kernel families only (gemm.hip: exact, register-staged MFMA, 128 x 128 LDS-DMA)
+constexpr unsigned EPI_SET_DROP = EPI_BIT(MAED_EPI_RESID_DROP_F32) | EPI_BIT(MAED_EPI_GELU_DROP) | EPI_BIT(MAED_EPI_MUL_DGELU_DROP);
 template <unsigned SET, int EPI = 0, typename F>
 static inline bool epilogue_switch(int epilogue, F&& f) {
-    static_assert((SET >> (MAED_EPI_ADD + 1)) == 0, "epilogue_switch walks MAED_EPI_STORE .. MAED_EPI_ADD: raise the bound below together with a new epilogue");
-    if constexpr (EPI > MAED_EPI_ADD) return false;
+    static_assert((SET >> (MAED_EPI_MUL_DGELU_DROP + 1)) == 0, "epilogue_switch walks MAED_EPI_STORE .. MAED_EPI_MUL_DGELU_DROP: raise the bound below together with a new epilogue");
+    if constexpr (EPI > MAED_EPI_MUL_DGELU_DROP) return false;
     else {
         if constexpr ((SET >> EPI) & 1u) { if (epilogue == EPI) { f(std::integral_constant<int, EPI>{}); return true; } }
         return epilogue_switch<SET, EPI + 1>(epilogue, f);

@@ -29,7 +29,9 @@ class MAED(nn.Module):
             self.encoder = resnet50(compute_dtype=compute_dtype, f32_matmul=backbone_f32_matmul)
         elif encoder.lower() == 'ste':
             self.encoder = vit_custom_resnet50_224_in21k(num_blocks, num_heads, st_mode, embed_dim=embed_dim, img_size=img_size,
-                                                         max_seqlen=max_seqlen, compute_dtype=compute_dtype, impl=impl)
+                                                         max_seqlen=max_seqlen, compute_dtype=compute_dtype, impl=impl,
+                                                         # the encoder's regularisers (maed.py:39 passes **kwargs on; the decoders take none of them)
+                                                         **{k: kwargs[k] for k in ("drop_rate", "drop_path_rate", "attn_drop_rate") if k in kwargs})
             # compute_dtype = float32: the backbone's own fp32 matmul engine (resnetv2.ResNetV2.f32_matmul); None = the process-wide mode
             self.encoder.patch_embed.backbone.f32_matmul = backbone_f32_matmul
         else:

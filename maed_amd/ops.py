@@ -403,6 +403,51 @@ def gemm_nt(A, B, epilogue=L.EPI_STORE, bias=None, out=None, out2=None, aux=None
     return (out, out2) if epilogue == L.EPI_GELU else out
 
 
+# ---- dropout / stochastic depth of the STE blocks (include/maed_hip.h "MASK DEFINITION") --------------------------------------------------------------------
+def new_block_seed(device, pinned=None):
+    """(seed, state, call_id) of one regularised block forward: a pinned int (eager only: tests, reproducibility); else the running step's device record and the
+    next call id (a captured step then replays with fresh masks, as ste_modes.dropout); else one draw from torch's CPU generator"""
+    if pinned is not None:
+        return int(pinned) & (2 ** 64 - 1), None, 0
+    st = DEVICE_STATE
+    if st is not None and st.dev.device == device:
+        return 0, st.dev, st.next_call_id()
+    return int(torch.randint(0, 2 ** 62, (1,), dtype=torch.int64).item()), None, 0
+
+
+def drop_args(reg, site_drop, site_path, group_rows):
+    """maed_drop_args of one site pair; reg = (drop, drop_path, seed, state tensor or None, call_id) of the block"""
+    drop, drop_path, seed, state, call_id = reg
+    return L.DropArgs(float(drop) if site_drop else 0.0, float(drop_path) if site_path else 0.0, site_drop, site_path, seed, _p(state), call_id, group_rows)
+
+
+def block_reg(reg):
+    drop, drop_path, seed, state, call_id = reg
+    return L.BlockReg(float(drop), float(drop_path), seed, _p(state), call_id)
+
+
+def gemm_nt_drop(A, B, epilogue, dargs, bias=None, out=None, out2=None, aux=None, impl=L.IMPL_AUTO):
+    """gemm_nt with the masked epilogues EPI_RESID_DROP_F32 / EPI_GELU_DROP / EPI_MUL_DGELU_DROP (maed_gemm_nt_drop); dargs: drop_args(...)"""
+    assert A.dim() == 2 and B.dim() == 2 and A.dtype == B.dtype and A.stride(1) == 1 and B.stride(1) == 1
+    M, K = A.shape
+    N = B.shape[0]
+    if out is None:
+        out = torch.empty(M, N, dtype=torch.float32 if epilogue == L.EPI_RESID_DROP_F32 else A.dtype, device=A.device)
+    if epilogue == L.EPI_GELU_DROP and out2 is None:
+        out2 = torch.empty_like(out)
+    check(L.lib().maed_gemm_nt_drop(_p(A), A.stride(0), _p(B), B.stride(0), M, N, K, dt_code(A.dtype), epilogue, _p(bias), _p(out), out.stride(0), _p(out2),
+                                    _p(aux), aux.stride(0) if aux is not None else 0, impl, C.byref(dargs), _stream()), "gemm_nt_drop")
+    return (out, out2) if epilogue == L.EPI_GELU_DROP else out
+
+
+def drop_scale_cast(x, out_dtype, dargs, out=None):
+    """out[out_dtype](rows, N) = frame mask * element mask * x[f32](rows, N) (maed_drop_scale_cast); the same call on a gradient is the backward"""
+    assert x.dim() == 2 and x.dtype == torch.float32 and x.is_contiguous()
+    out = torch.empty(x.shape, dtype=out_dtype, device=x.device) if out is None else out
+    check(L.lib().maed_drop_scale_cast(_p(x), _p(out), x.shape[0], x.shape[1], dt_code(out_dtype), C.byref(dargs), _stream()), "drop_scale_cast")
+    return out
+
+
 def split_planes(x):
     """(hi, lo) bf16 planes of an fp32 tensor: hi = bf16(x), lo = bf16(x - hi) -- the operand format of gemm_nt_planes (csrc/gemm_x3p.hip)"""
     x = _c(x)
@@ -778,6 +823,7 @@ class EmbedAddFn(torch.autograd.Function):
 _TWIN = [None, None, None]      # [weakref to dx, its compute-dtype copy, chain index of the block that left it (Block._chain_index, None if unknown)]
 TWIN_HITS = [0, 0]   # [hits, misses] -- diagnostics
 _TWIN_WARNED = [False]
+_REG_TWIN_WARNED = [False]
 
 
 # ---- parameter gradients written straight into .grad by a backward kernel, without autograd's AccumulateGrad ------------------------------------------------
@@ -852,8 +898,19 @@ class STEBlockFn(ReportingFn):
         d = L.BlockDims(*dims)
         y = torch.empty_like(x)
         # fp32 forward, bf16 twins for the backward (set_float32_backward_precision("bf16")): the arena has the bf16 block's layout, the backward its dims
+        # dropout / stochastic depth: training mode with a non-zero rate and a backward to come -- everything else is the identity on today's entry points
+        rates = (getattr(block, "drop", 0.0), getattr(block, "drop_path_prob", 0.0))
+        regd = block.training and (rates[0] > 0.0 or rates[1] > 0.0) and ReportingFn.will_run_backward(ctx)
         twin = block.compute_dtype == torch.float32 and bwd_twin() and ReportingFn.will_run_backward(ctx) and dims[7] != L.IMPL_VALU and dims[2] % 8 == 0 and dims[5] % 8 == 0 \
             and dims[2] == 64 * dims[3]      # (the twin forward exists for head size 64 only: other head sizes take the forward's engine for their backward)
+        if twin and regd:       # no masks in the twin forward: the regularised block runs forward and backward on the forward's engine
+            twin = False
+            if not _REG_TWIN_WARNED[0]:
+                _REG_TWIN_WARNED[0] = True
+                import warnings
+                warnings.warn("maed_amd: a block with dropout / stochastic depth does not take the bf16-twin forward (set_float32_backward_precision('bf16')); "
+                              "its backward runs on the forward's fp32 engine", RuntimeWarning, stacklevel=2)
+        ctx.reg = None
         if twin:
             dims = dims[:6] + (BF16,) + dims[7:]
             d16 = L.BlockDims(*dims)
@@ -868,8 +925,12 @@ class STEBlockFn(ReportingFn):
             pr = block._c_params(block.compute_dtype)
             saved = _aligned_bytes(lib.maed_ste_block_saved_bytes(C.byref(d)), x.device)
             # no backward will follow (torch.no_grad / nothing requires grad): the inference entry point leaves out what only the backward reads
-            entry = lib.maed_ste_block_fwd if ReportingFn.will_run_backward(ctx) else lib.maed_ste_block_infer
-            check(entry(C.byref(d), C.byref(pr), _p(x), _p(y), _p(saved), _stream()), "ste_block_fwd")
+            if regd:
+                ctx.reg = rates + new_block_seed(x.device, getattr(block, "drop_seed", None))
+                check(lib.maed_ste_block_fwd_reg(C.byref(d), C.byref(pr), _p(x), _p(y), _p(saved), C.byref(block_reg(ctx.reg)), _stream()), "ste_block_fwd_reg")
+            else:
+                entry = lib.maed_ste_block_fwd if ReportingFn.will_run_backward(ctx) else lib.maed_ste_block_infer
+                check(entry(C.byref(d), C.byref(pr), _p(x), _p(y), _p(saved), _stream()), "ste_block_fwd")
         ctx.block, ctx.dims, ctx.bdt = block, dims, (torch.bfloat16 if twin else block.compute_dtype)
         ctx.save_for_backward(x, saved)
         # a hand-off left by the LAST block of an earlier backward pass (nobody consumes block 0's) is stale once a new forward runs: dropping it here frees its tensor
@@ -908,8 +969,12 @@ class STEBlockFn(ReportingFn):
             TWIN_HITS[0 if tw_in is not None else 1] += 1
         _TWIN[0], _TWIN[1], _TWIN[2] = None, None, None
         tw_out = torch.empty(dy.shape, dtype=cdt, device=dy.device) if cdt != torch.float32 else None
-        check(lib.maed_ste_block_bwd(C.byref(d), C.byref(pr), C.byref(gr), _p(x), _p(dy), _p(dx), _p(saved), _p(scratch),
-                                     _p(tw_in), _p(tw_out), _stream()), "ste_block_bwd")
+        if ctx.reg is not None:      # the forward's masks again (same seed / call id); the branch gradients are masked copies made inside: the handed-along twin is not used
+            check(lib.maed_ste_block_bwd_reg(C.byref(d), C.byref(pr), C.byref(gr), _p(x), _p(dy), _p(dx), _p(saved), _p(scratch), _p(tw_out),
+                                             C.byref(block_reg(ctx.reg)), _stream()), "ste_block_bwd_reg")
+        else:
+            check(lib.maed_ste_block_bwd(C.byref(d), C.byref(pr), C.byref(gr), _p(x), _p(dy), _p(dx), _p(saved), _p(scratch),
+                                         _p(tw_in), _p(tw_out), _stream()), "ste_block_bwd")
         if tw_out is not None:
             _TWIN[0], _TWIN[1], _TWIN[2] = weakref.ref(dx), tw_out, getattr(block, "_chain_index", None)
         block._pending_backwards -= 1

@@ -10,6 +10,7 @@ the benchmarked path and are composed here from the same libmaed_hip kernels, on
     TemporalAttnFn     maed_attn_temporal_fwd / _bwd
     TokenMeanFn        maed_st_colmean                          'temporal' mode's mean over the tokens of a frame
     MlpFn              fc1+GELU and fc2 with the fused epilogues (GELU', bias) of the fused block
+    DropScaleFn        maed_drop_scale_cast                     Dropout / DropPath masks on fp32 rows (the five sites of a regularised block)
 
 'coupling' attends over the T*P tokens of a clip.  Frames of a clip are contiguous rows, and the reference's reshape_T
 (:180-189) orders a clip's tokens (t, p), i.e. exactly the row-major order of the (T, P, 3C) qkv rows of that clip -- so
@@ -128,15 +129,43 @@ class LinearTokFn(_ApplyMixin, torch.autograd.Function):
         return dx, dW, db, None, None, None, None
 
 
-class MlpFn(torch.autograd.Function):
-    """fc2(GELU_erf(fc1(h))) (vision_transformer.py:96-112); h compute dtype (M,C) -> fp32 (M,C)"""
+class DropScaleFn(torch.autograd.Function):
+    """y = frame mask * element mask * x on fp32 rows (rows, N): nn.Dropout / DropPath of a regularised block as ONE pass (sites 1 + 2: the attention branch).
+    reg = (drop, drop_path, seed, state, call_id) of the block (ops.new_block_seed); the mask is recomputed in the backward, not stored."""
 
     @staticmethod
-    def forward(ctx, h, w1, b1, w2, b2, cache):
+    def forward(ctx, x, reg, site_drop, site_path, group_rows, out_dtype):
+        ctx.args = (reg, site_drop, site_path, group_rows)
+        return ops.drop_scale_cast(_as(x, torch.float32), out_dtype, ops.drop_args(reg, site_drop, site_path, group_rows))
+
+    @staticmethod
+    def backward(ctx, dy):
+        return ops.drop_scale_cast(_as(dy, torch.float32), torch.float32, ops.drop_args(*ctx.args)), None, None, None, None, None
+
+
+class MlpFn(torch.autograd.Function):
+    """fc2(GELU_erf(fc1(h))) (vision_transformer.py:96-112); h compute dtype (M,C) -> fp32 (M,C).
+    reg (a regularised block, ops.new_block_seed): Dropout on the hidden activation in fc1's epilogue (site 3); Dropout on the output and DropPath (sites 4 + 5) in
+    fc2's epilogue together with the residual add when `resid` (fp32 (M,C)) is given -- the result is then resid + masked branch -- else as one pass over the output."""
+
+    @staticmethod
+    def forward(ctx, h, w1, b1, w2, b2, cache, resid=None, reg=None, group_rows=1):
         (w1c, w1t), (w2c, w2t) = cache.get([w1, w2], h.dtype)
         h = _as(h, h.dtype)
-        act, pre = ops.gemm_nt(h, w1c, L.EPI_GELU, bias=b1)
-        y = ops.gemm_nt(act, w2c, L.EPI_STORE_F32, bias=b2)
+        ctx.reg, ctx.group_rows, ctx.has_resid = reg, group_rows, resid is not None
+        if reg is not None:
+            a3, a45 = ops.drop_args(reg, 3, 0, group_rows), ops.drop_args(reg, 4, 5, group_rows)
+            act, pre = ops.gemm_nt_drop(h, w1c, L.EPI_GELU_DROP, a3, bias=b1) if reg[0] > 0.0 else ops.gemm_nt(h, w1c, L.EPI_GELU, bias=b1)
+            if resid is not None:
+                y = ops.gemm_nt_drop(act, w2c, L.EPI_RESID_DROP_F32, a45, bias=b2, aux=_as(resid, torch.float32))
+            else:
+                y = ops.gemm_nt(act, w2c, L.EPI_STORE_F32, bias=b2)
+                ops.drop_scale_cast(y, torch.float32, a45, out=y)
+        else:
+            act, pre = ops.gemm_nt(h, w1c, L.EPI_GELU, bias=b1)
+            y = ops.gemm_nt(act, w2c, L.EPI_STORE_F32, bias=b2)
+            if resid is not None:
+                y = y + resid
         ctx.save_for_backward(h, act, pre)
         ctx.wts = (w1t, w2t)
         return y
@@ -145,12 +174,22 @@ class MlpFn(torch.autograd.Function):
     def backward(ctx, dy):
         h, act, pre = ctx.saved_tensors
         w1t, w2t = ctx.wts
+        if ctx.reg is not None:      # the branch gradient is the MASKED copy of dy (sites 4 + 5) in the compute dtype; the residual path keeps dy itself
+            reg, gr = ctx.reg, ctx.group_rows
+            dym = ops.drop_scale_cast(_as(dy, torch.float32), h.dtype, ops.drop_args(reg, 4, 5, gr))
+            dW2, db2 = _wgrad(dym, act, True)
+            dpre = (ops.gemm_nt_drop(dym, w2t, L.EPI_MUL_DGELU_DROP, ops.drop_args(reg, 3, 0, gr), aux=pre) if reg[0] > 0.0
+                    else ops.gemm_nt(dym, w2t, L.EPI_MUL_DGELU, aux=pre))
+            dW1, db1 = _wgrad(dpre, h, True)
+            dh = ops.gemm_nt(dpre, w1t, L.EPI_STORE) if ctx.needs_input_grad[0] else None
+            return (dh, dW1, db1, dW2, db2, None, dy if ctx.has_resid else None, None, None)[:len(ctx.needs_input_grad)]
+        d_res = dy if ctx.has_resid else None
         dy = _as(dy, h.dtype)
         dW2, db2 = _wgrad(dy, act, True)
         dpre = ops.gemm_nt(dy, w2t, L.EPI_MUL_DGELU, aux=pre)            # (dy W2) * GELU'(fc1 pre-activation)
         dW1, db1 = _wgrad(dpre, h, True)
         dh = ops.gemm_nt(dpre, w1t, L.EPI_STORE) if ctx.needs_input_grad[0] else None
-        return dh, dW1, db1, dW2, db2, None
+        return (dh, dW1, db1, dW2, db2, None, d_res, None, None)[:len(ctx.needs_input_grad)]
 
 
 class SpatialAttnFn(torch.autograd.Function):
@@ -344,8 +383,17 @@ def block(blk, x, seqlen):
     Fr, P, C_ = x.shape
     cd = blk.compute_dtype
     x = x.float()
+    # dropout / stochastic depth (training mode, a non-zero rate): the five sites of the fused block with the same seeds and indices (include/maed_hip.h "MASK DEFINITION")
+    reg = None
+    if blk.training and (blk.drop > 0.0 or blk.drop_path_prob > 0.0) and torch.is_grad_enabled():
+        reg = (blk.drop, blk.drop_path_prob) + ops.new_block_seed(x.device, blk.drop_seed)
     h = LayerNormFn.apply(x.reshape(-1, C_), blk.norm1.weight, blk.norm1.bias, blk.norm1.eps, cd).view(Fr, P, C_)
-    x = x + attention(blk.attn, h, seqlen, cd, blk.impl)          # 'temporal': (F,1,C) broadcasts over the tokens
+    a = attention(blk.attn, h, seqlen, cd, blk.impl)              # 'temporal': (F,1,C) broadcasts over the tokens
+    if reg is not None:     # sites 1 + 2 on the branch as the reference sees it: (F*P, C) rows, P rows per frame -- 'temporal': (F, C) rows, one per frame
+        a = DropScaleFn.apply(a.reshape(-1, C_), reg, 1, 2, a.shape[1], torch.float32).view(a.shape)
+    x = x + a
     h = LayerNormFn.apply(x.reshape(-1, C_), blk.norm2.weight, blk.norm2.bias, blk.norm2.eps, cd)
+    if reg is not None:     # sites 3, 4 + 5 and the residual add in the MLP GEMMs' epilogues
+        return MlpFn.apply(h, blk.mlp.fc1.weight, blk.mlp.fc1.bias, blk.mlp.fc2.weight, blk.mlp.fc2.bias, blk.mlp._cache, x.reshape(-1, C_), reg, P).view(Fr, P, C_)
     m = MlpFn.apply(h, blk.mlp.fc1.weight, blk.mlp.fc1.bias, blk.mlp.fc2.weight, blk.mlp.fc2.bias, blk.mlp._cache)
     return x + m.view(Fr, P, C_)

@@ -37,8 +37,44 @@ def _needs_grad(*tensors):
     return torch.is_grad_enabled() and any(t is not None and t.requires_grad for t in tensors)
 
 
+_UNSUPPORTED_RATES = ("{what} is not implemented: attention-probability dropout touches every attention kernel family and qk_scale also the inference entry "
+                      "point (docs/design/14_ste_regularisation.md, out of scope); drop_rate / drop_path_rate / Block(drop=, drop_path=) are supported")
+
+
+def _check_attention_knobs(qk_scale, attn_drop):
+    if qk_scale is not None:
+        raise NotImplementedError(_UNSUPPORTED_RATES.format(what=f"qk_scale={qk_scale}"))
+    if attn_drop:
+        raise NotImplementedError(_UNSUPPORTED_RATES.format(what=f"attn_drop / attn_drop_rate={attn_drop}"))
+
+
+def _check_rate(name, p):
+    if not 0.0 <= p < 1.0:
+        raise ValueError(f"{name} must be in [0, 1), got {p}")
+    return float(p)
+
+
+class DropPath(nn.Module):
+    """ops/drop.py DropPath (stochastic depth per sample = per frame): identity in eval; in training a whole frame's branch is zeroed with probability drop_prob and
+    the survivors are scaled by 1 / (1 - drop_prob).  Inside a Block the mask rides in the branch GEMM's epilogue (ops.STEBlockFn / ste_modes.block); called on its
+    own it runs the library's mask kernel on fp32 rows."""
+
+    def __init__(self, drop_prob=None):
+        super().__init__()
+        self.drop_prob = _check_rate("drop_prob", drop_prob or 0.0)
+
+    def forward(self, x):
+        if not self.training or self.drop_prob == 0.0:
+            return x
+        reg = (0.0, self.drop_prob) + ops.new_block_seed(x.device)
+        return ste_modes.DropScaleFn.apply(x.reshape(x.shape[0], -1), reg, 0, 2, 1, torch.float32).view(x.shape)
+
+    def extra_repr(self):
+        return f"drop_prob={self.drop_prob}"
+
+
 class Mlp(nn.Module):
-    """vision_transformer.py:96-112: fc2(GELU_erf(fc1(x))); dropouts are rate 0 on this path."""
+    """vision_transformer.py:96-112: fc2(GELU_erf(fc1(x))) with Dropout(drop) behind the activation and behind fc2 (training mode; sites 3 and 4 of the mask definition)."""
 
     def __init__(self, in_features, hidden_features=None, out_features=None, act_layer=nn.GELU, drop=0.):
         super().__init__()
@@ -47,14 +83,15 @@ class Mlp(nn.Module):
         self.fc1 = nn.Linear(in_features, hidden_features)
         self.act = act_layer()
         self.fc2 = nn.Linear(hidden_features, out_features)
-        self.drop = nn.Dropout(drop)
+        self.drop = nn.Dropout(_check_rate("drop", drop))
         self._cache = ops.WeightCache()
 
     def forward(self, x, compute_dtype=torch.float32):
         """Stand-alone (inference) use; inside a Block the MLP runs fused in maed_ste_block_fwd."""
         shp = x.shape
         if _needs_grad(x, self.fc1.weight):     # stand-alone differentiable use: the staged Function (inside a Block the MLP runs fused)
-            y = ste_modes.MlpFn.apply(x.reshape(-1, shp[-1]).to(compute_dtype), self.fc1.weight, self.fc1.bias, self.fc2.weight, self.fc2.bias, self._cache)
+            reg = (self.drop.p, 0.0) + ops.new_block_seed(x.device) if (self.training and self.drop.p > 0.0) else None
+            y = ste_modes.MlpFn.apply(x.reshape(-1, shp[-1]).to(compute_dtype), self.fc1.weight, self.fc1.bias, self.fc2.weight, self.fc2.bias, self._cache, None, reg, 1)
             return y.reshape(*shp[:-1], -1)
         (w1, _), (w2, _) = self._cache.get([self.fc1.weight, self.fc2.weight], compute_dtype)
         a = x.reshape(-1, shp[-1]).to(compute_dtype)
@@ -73,8 +110,7 @@ class Attention(nn.Module):
             raise NotImplementedError(st_mode)       # the reference raises at forward time (:175)
         if dim % num_heads or dim // num_heads not in L.HEAD_DIMS:
             raise NotImplementedError(f"head size dim/num_heads must be one of {L.HEAD_DIMS} (dim={dim}, heads={num_heads})")
-        if qk_scale is not None or attn_drop or proj_drop:
-            raise NotImplementedError("qk_scale / attention dropout are not used on the MAED path")
+        _check_attention_knobs(qk_scale, attn_drop)
         self.num_heads = num_heads
         self.scale = (dim // num_heads) ** -0.5
         self.proj = nn.Linear(dim, dim)
@@ -83,7 +119,7 @@ class Attention(nn.Module):
             self.ts_attn = nn.Linear(dim * 2, dim * 2)
         self.qkv = nn.Linear(dim, dim * 3, bias=qkv_bias)
         self.attn_drop = nn.Dropout(attn_drop)
-        self.proj_drop = nn.Dropout(proj_drop)
+        self.proj_drop = nn.Dropout(_check_rate("proj_drop", proj_drop))      # (applied by the Block: site 1 of the mask definition, in the proj GEMM's epilogue)
         self._cache = ops.WeightCache()
 
     def forward(self, x, seqlen=1, compute_dtype=torch.float32, impl=L.IMPL_AUTO, return_parts=False):
@@ -119,12 +155,14 @@ class Block(nn.Module):
                  drop_path=0., act_layer=nn.GELU, norm_layer=nn.LayerNorm, st_mode='vanilla',
                  compute_dtype=torch.bfloat16, impl=L.IMPL_AUTO):
         super().__init__()
-        if drop or drop_path:
-            raise NotImplementedError("dropout / stochastic depth are rate 0 on the MAED path (vision_transformer.py:568)")
+        _check_attention_knobs(qk_scale, attn_drop)
+        # rates of the five mask sites (include/maed_hip.h "MASK DEFINITION"): `drop` at sites 1, 3, 4 (proj_drop, the two Mlp dropouts), `drop_path` at sites 2, 5.
+        # drop_seed: None = the running step's device record (ops.DEVICE_STATE) or one draw from torch's CPU generator per forward; an int pins the block seed (eager only)
+        self.drop, self.drop_path_prob, self.drop_seed = _check_rate("drop", drop), _check_rate("drop_path", drop_path), None
         self.norm1 = norm_layer(dim)
         self.attn = Attention(dim, num_heads=num_heads, qkv_bias=qkv_bias, qk_scale=qk_scale, attn_drop=attn_drop,
                               proj_drop=drop, st_mode=st_mode)
-        self.drop_path = nn.Identity()
+        self.drop_path = DropPath(drop_path) if drop_path > 0. else nn.Identity()
         self.norm2 = norm_layer(dim)
         self.mlp = Mlp(in_features=dim, hidden_features=int(dim * mlp_ratio), act_layer=act_layer, drop=drop)
         self.dim, self.num_heads, self.hidden = dim, num_heads, int(dim * mlp_ratio)
@@ -247,8 +285,8 @@ class VisionTransformer(nn.Module):
         super().__init__()
         if hybrid_backbone is None:
             raise NotImplementedError("only the hybrid (CNN feature map) input stage is on the MAED path")
-        if drop_rate or attn_drop_rate or drop_path_rate:
-            raise NotImplementedError("dropout rates are 0 on the MAED path (vision_transformer.py:568)")
+        _check_attention_knobs(qk_scale, attn_drop_rate)
+        drop_rate, drop_path_rate = _check_rate("drop_rate", drop_rate), _check_rate("drop_path_rate", drop_path_rate)
         self.num_classes = num_classes
         self.num_features = self.embed_dim = embed_dim
         self.compute_dtype = compute_dtype
@@ -257,10 +295,11 @@ class VisionTransformer(nn.Module):
         self.cls_token = nn.Parameter(torch.zeros(1, 1, embed_dim))
         self.pos_embed = nn.Parameter(torch.zeros(1, num_patches + 1, embed_dim))
         self.pos_drop = nn.Dropout(p=drop_rate)
+        dpr = [x.item() for x in torch.linspace(0, drop_path_rate, depth)]      # stochastic depth decay rule (:337)
         self.blocks = nn.ModuleList([
-            Block(dim=embed_dim, num_heads=num_heads, mlp_ratio=mlp_ratio, qkv_bias=qkv_bias, qk_scale=qk_scale,
-                  norm_layer=norm_layer, st_mode=st_mode, compute_dtype=compute_dtype, impl=impl)
-            for _ in range(depth)])
+            Block(dim=embed_dim, num_heads=num_heads, mlp_ratio=mlp_ratio, qkv_bias=qkv_bias, qk_scale=qk_scale, drop=drop_rate, attn_drop=attn_drop_rate,
+                  drop_path=dpr[i], norm_layer=norm_layer, st_mode=st_mode, compute_dtype=compute_dtype, impl=impl)
+            for i in range(depth)])
         for i, blk in enumerate(self.blocks):
             blk._chain_index = i        # position in the chain: ops.STEBlockFn's residual-gradient hand-off knows which block a copy was left for
         self.norm = norm_layer(embed_dim)
@@ -299,6 +338,7 @@ class VisionTransformer(nn.Module):
             tok = ops.EmbedAddFn.apply(patch, self.cls_token, self.pos_embed, self.temp_embed, seqlen)
         else:
             tok = ops.EmbedAddFn.apply(patch, self.cls_token, self.pos_embed, self._no_temp_embed, 1)
+        tok = ste_modes.dropout(tok, self.pos_drop.p, self.training)      # pos_drop (:401)
         twins = ops.TWIN_FORWARDS[0]
         for blk in self.blocks:
             tok = blk(tok, seqlen)
