@@ -630,6 +630,41 @@ int maed_adam_step(float* p, const float* g, float* m, float* v, void* shadow_bf
 int maed_adam_step_dev(float* p, const float* g, float* m, float* v, void* shadow_bf16, int64_t n, const maed_train_state* state,
                        float beta1, float beta2, float eps, float weight_decay, float gscale, void* stream);
 
+/* ---- optimizers: SGD momentum, AdamW, global-norm clipping, per-segment hyper-parameters (lib/utils/utils.py:120-135; docs/design/15_optimizers.md) - */
+/* Global L2 norm of a flat fp32 gradient arena, sqnorm = sum((gscale * g[i])^2), and the coefficient of torch.nn.utils.clip_grad_norm_ -- on the device, never
+ * seen by the host.  Two launches in a fixed order (per-workgroup partial sums, then one workgroup that adds the partials in fp64): no floating-point atomics, the
+ * same bits on every call.  For n <= 2^27 an element's square passes through at most 78 fp32 additions (<= 256), all terms are non-negative: relative error of
+ * sqnorm <= 78 * 2^-24, of norm half that.  `partials` is caller-owned workspace of maed_grad_norm_partials() floats (a constant); `out` is this 16-byte record:
+ *   norm = sqrt(sqnorm);  coef = max_norm > 0 ? min(1, max_norm / (norm + 1e-6f)) : 1;  nonfinite = 1 if sqnorm is inf or NaN (coef is then what the formula gives) */
+typedef struct { float sqnorm, norm, coef; uint32_t nonfinite; } maed_clip_state;
+size_t maed_grad_norm_partials(void);
+int maed_grad_norm(const float* g, int64_t n, float gscale, float max_norm, float* partials, maed_clip_state* out, void* stream);
+
+/* One step kernel for three update rules (torch's definitions), g' = g * gscale * (clip ? clip->coef : 1) with coef read from device memory when the kernel runs:
+ *   MAED_OPT_ADAM  (torch.optim.Adam; maed_adam_step's arithmetic):  gr = wd*p + g';  m = b1 m + (1-b1) gr;  v = b2 v + (1-b2) gr^2;
+ *                                                                    p -= (lr/bc1) m / (sqrt(v)/sqrt(bc2) + eps)
+ *   MAED_OPT_ADAMW (torch.optim.AdamW):                              p *= 1 - lr*wd;  then the ADAM update with gr = g'
+ *   MAED_OPT_SGD   (torch.optim.SGD, dampening 0):                   d = g' + wd*p;  momentum != 0: buf = momentum*buf + d;  d = nesterov ? d + momentum*buf : buf;
+ *                                                                    p -= lr*d       (buf = m; a zero buffer makes the first step copy the gradient)
+ * m, v: Adam / AdamW need both; SGD needs m only when momentum != 0 (v is ignored, both may be NULL).  shadow_bf16 as in maed_adam_step.
+ * state != NULL: lr, bias_corr1, bias_corr2 are read from the device record (as maed_adam_step_dev), also with a segment table.
+ * segments != NULL: a device array of n_segments entries sorted by `begin`, pairwise disjoint, begin % 4 == 0, 0 <= begin <= end (end is clamped to n).  Elements
+ * [begin, end) take the entry's lr and weight_decay; elements outside every segment are neither read nor written; an entry with begin == end is legal; an end that
+ * is not a multiple of 4 is honoured exactly.  One launch serves per-group hyper-parameters, no-decay groups and "skip the tensors without a gradient". */
+enum { MAED_OPT_ADAM = 0, MAED_OPT_ADAMW = 1, MAED_OPT_SGD = 2 };
+typedef struct { int64_t begin, end; float lr, weight_decay; } maed_opt_segment;
+typedef struct {
+    int kind;
+    float lr, beta1, beta2, eps, weight_decay, bias_corr1, bias_corr2, momentum;
+    int nesterov;
+    float gscale;
+    const maed_train_state* state;
+    const maed_clip_state* clip;
+    const maed_opt_segment* segments;
+    int n_segments;
+} maed_opt_args;
+int maed_opt_step(float* p, const float* g, float* m, float* v, void* shadow_bf16, int64_t n, const maed_opt_args* a, void* stream);
+
 /* ---- gradient all-reduce: RCCL over xGMI on a side HIP stream (train.py:113,182 DDP/NCCL) ----------------------- */
 /* One communicator per process.  RCCL is bound at run time from the library the host names (NULL = "librccl.so.1");
  * pass the copy PyTorch-ROCm already loaded so the process holds one RCCL.  unique_id: MAED_COMM_ID_BYTES made by

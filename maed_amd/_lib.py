@@ -61,6 +61,15 @@ class BlockReg(C.Structure):
     _fields_ = [("drop", f32), ("drop_path", f32), ("seed", C.c_uint64), ("state", vp), ("call_id", C.c_uint64)]
 
 
+OPT_ADAM, OPT_ADAMW, OPT_SGD = 0, 1, 2     # maed_opt_args.kind
+
+
+class OptArgs(C.Structure):
+    """maed_opt_args (include/maed_hip.h): update rule, scalars and the optional device-side inputs of maed_opt_step"""
+    _fields_ = [("kind", i32), ("lr", f32), ("beta1", f32), ("beta2", f32), ("eps", f32), ("weight_decay", f32), ("bias_corr1", f32), ("bias_corr2", f32),
+                ("momentum", f32), ("nesterov", i32), ("gscale", f32), ("state", vp), ("clip", vp), ("segments", vp), ("n_segments", i32)]
+
+
 class SmplParams(C.Structure):
     _fields_ = [(n, vp) for n in ["v_template", "shapedirs", "posedirs", "J_template", "J_shapedirs", "lbs_weights", "parents"]]
 
@@ -186,6 +195,9 @@ SIGNATURES = {
     "maed_weight_refresh": (i32, [vp, i32, i32, i32, vp]),
     "maed_adam_step": (i32, [vp, vp, vp, vp, vp, i64, f32, f32, f32, f32, f32, f32, f32, f32, vp]),
     "maed_adam_step_dev": (i32, [vp, vp, vp, vp, vp, i64, vp, f32, f32, f32, f32, f32, vp]),
+    "maed_grad_norm_partials": (C.c_size_t, []),
+    "maed_grad_norm": (i32, [vp, i64, f32, f32, vp, vp, vp]),
+    "maed_opt_step": (i32, [vp, vp, vp, vp, vp, i64, C.POINTER(OptArgs), vp]),
     "maed_clip_preprocess_workspace": (C.c_size_t, [i32, i32, i32]),
     "maed_clip_preprocess": (i32, [vp, i64, vp, vp, vp, vp, i32, i32, i32, i32, C.POINTER(f32), i32, i32, vp, vp, C.c_size_t, vp]),
     "maed_render_mesh_workspace": (C.c_size_t, [i32, i32, i32, i32, i32, i32]),

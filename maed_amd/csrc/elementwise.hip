@@ -810,3 +810,195 @@ extern "C" int maed_adam_step_dev(float* p, const float* g, float* m, float* v, 
     MAED_CHECK_LAUNCH("adam_step_dev");
     return MAED_OK;
 }
+
+// ---------------------------------------------------------------------------------------------------
+// Global gradient norm: sum((gscale * g[i])^2) in two stages with a fixed order (no atomics), then the clip coefficient into a 16-byte device record
+// ---------------------------------------------------------------------------------------------------
+// Stage 1: at most GN_BLOCKS workgroups; thread t of workgroup b takes the float4s b * 256 + t, + grid * 256, ... into four fp32 accumulators (one per component),
+// so which additions an element's square passes through depends on n alone.  Longest fp32 chain for n <= 2^27: ceil(2^25 / (2048 * 256)) = 64 accumulations, + 3 (the
+// n % 4 tail elements, thread 0 of workgroup 0), + 2 (the four accumulators pairwise), + 6 (wave butterfly), + 3 (four waves) = 78.  Stage 2 sums the partials in fp64.
+#define GN_BLOCKS 2048
+__global__ __launch_bounds__(256) void grad_sqnorm_partial_kernel(const float* __restrict__ g, int64_t n, float gscale, float* __restrict__ partials) {
+    __shared__ float ws[4];
+    const int64_t n4 = n >> 2, stride = (int64_t)gridDim.x * 256;
+    float acc[4] = {0.f, 0.f, 0.f, 0.f};
+    int64_t q = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    for (; q + 3 * stride < n4; q += 4 * stride) {        // four independent 16-byte loads in flight, accumulated in index order
+        float x0[4], x1[4], x2[4], x3[4];
+        ld4(g + q * 4, x0); ld4(g + (q + stride) * 4, x1); ld4(g + (q + 2 * stride) * 4, x2); ld4(g + (q + 3 * stride) * 4, x3);
+#pragma unroll
+        for (int j = 0; j < 4; ++j) {
+            float x = x0[j] * gscale; acc[j] = fmaf(x, x, acc[j]);
+            x = x1[j] * gscale; acc[j] = fmaf(x, x, acc[j]);
+            x = x2[j] * gscale; acc[j] = fmaf(x, x, acc[j]);
+            x = x3[j] * gscale; acc[j] = fmaf(x, x, acc[j]);
+        }
+    }
+    for (; q < n4; q += stride) {
+        float x0[4];
+        ld4(g + q * 4, x0);
+#pragma unroll
+        for (int j = 0; j < 4; ++j) { const float x = x0[j] * gscale; acc[j] = fmaf(x, x, acc[j]); }
+    }
+    if (blockIdx.x == 0 && threadIdx.x == 0)
+        for (int64_t i = n4 * 4; i < n; ++i) { const float x = g[i] * gscale; acc[0] = fmaf(x, x, acc[0]); }
+    const float s = wave_sum((acc[0] + acc[1]) + (acc[2] + acc[3]));
+    if ((threadIdx.x & 63) == 0) ws[threadIdx.x >> 6] = s;
+    __syncthreads();
+    if (threadIdx.x == 0) partials[blockIdx.x] = ((ws[0] + ws[1]) + ws[2]) + ws[3];
+}
+
+// Stage 2, one workgroup: the partials in fp64 (strided per thread, then a fixed LDS tree), norm and torch.nn.utils.clip_grad_norm_'s coefficient
+__global__ __launch_bounds__(256) void grad_norm_finalize_kernel(const float* __restrict__ partials, int count, float max_norm, maed_clip_state* __restrict__ out) {
+    __shared__ double sh[256];
+    const int t = (int)threadIdx.x;
+    double s = 0.0;
+    for (int i = t; i < count; i += 256) s += (double)partials[i];
+    sh[t] = s;
+    __syncthreads();
+    for (int o = 128; o > 0; o >>= 1) {
+        if (t < o) sh[t] += sh[t + o];
+        __syncthreads();
+    }
+    if (t == 0) {
+        const float sq = (float)sh[0], norm = sqrtf(sq);
+        float coef = 1.f;
+        if (max_norm > 0.f) {
+            const float c = max_norm / (norm + 1e-6f);
+            coef = c > 1.f ? 1.f : c;                      // (a NaN norm stays NaN, as torch.clamp(max=1) leaves it)
+        }
+        out->sqnorm = sq;
+        out->norm = norm;
+        out->coef = coef;
+        out->nonfinite = (__float_as_uint(sq) & 0x7f800000u) == 0x7f800000u ? 1u : 0u;
+    }
+}
+
+extern "C" size_t maed_grad_norm_partials(void) { return GN_BLOCKS; }
+
+extern "C" int maed_grad_norm(const float* g, int64_t n, float gscale, float max_norm, float* partials, maed_clip_state* out, void* stream) {
+    MAED_CHECK_ARG(partials && out && (g || n == 0) && n >= 0, MAED_ERR_ARG, "grad_norm: null pointer or negative size");
+    MAED_CHECK_ARG(is_aligned(g, 16) && is_aligned(partials, 4) && is_aligned(out, 4), MAED_ERR_ALIGN, "grad_norm: the gradient arena must be 16-B aligned");
+    const int64_t wgs = ((n >> 2) + 255) / 256;
+    const int blocks = (int)(wgs < 1 ? 1 : wgs > GN_BLOCKS ? GN_BLOCKS : wgs);
+    hipLaunchKernelGGL(grad_sqnorm_partial_kernel, dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream, g, n, gscale, partials);
+    MAED_CHECK_LAUNCH("grad_norm (partials)");
+    hipLaunchKernelGGL(grad_norm_finalize_kernel, dim3(1), dim3(256), 0, (hipStream_t)stream, (const float*)partials, blocks, max_norm, out);
+    MAED_CHECK_LAUNCH("grad_norm (finalize)");
+    return MAED_OK;
+}
+
+// ---------------------------------------------------------------------------------------------------
+// The general optimizer step (maed_opt_step): Adam / AdamW / SGD, optional clip coefficient and step scalars from device memory, optional segment table
+// ---------------------------------------------------------------------------------------------------
+struct OptK {
+    float lr, b1, b2, eps, wd, bc1, bc2, momentum;
+    int nesterov;
+    float gscale;
+    const maed_train_state* st;
+    const maed_clip_state* clip;
+    const maed_opt_segment* seg;
+    int nseg;
+};
+struct OptC { float lr, wd, step, rbc2, decay, b1, b2, eps, momentum, gs; int nesterov; };
+
+// one element; the MAED_OPT_ADAM arithmetic is adam_kernel's, expression for expression
+template <int KIND, bool MOM>
+__device__ __forceinline__ void opt_update(float& p, float g, float& m, float& v, const OptC& c) {
+    if (KIND == MAED_OPT_SGD) {
+        float d = fmaf(c.wd, p, g * c.gs);
+        if (MOM) {
+            m = c.momentum * m + d;
+            d = c.nesterov ? d + c.momentum * m : m;
+        }
+        p -= c.lr * d;
+    } else {
+        float gr;
+        if (KIND == MAED_OPT_ADAMW) { p *= c.decay; gr = g * c.gs; }
+        else gr = fmaf(c.wd, p, g * c.gs);
+        m = c.b1 * m + (1.f - c.b1) * gr;
+        v = c.b2 * v + (1.f - c.b2) * gr * gr;
+        p -= c.step * m / (sqrtf(v) * c.rbc2 + c.eps);
+    }
+}
+
+// One thread per 4 elements of [0, n).  With a segment table (sorted by begin, disjoint, begin % 4 == 0) a thread's 4 elements lie in at most one segment: the
+// workgroup's first candidate comes from a binary search by its base index (the same in every lane: scalar loads), a thread then walks forward from there.
+template <int KIND, bool MOM>
+__global__ __launch_bounds__(256) void opt_kernel(float* __restrict__ p, const float* __restrict__ g, float* __restrict__ m, float* __restrict__ v,
+                                                  bf16* __restrict__ shadow, int64_t n, OptK a) {
+    constexpr bool ADAMS = KIND != MAED_OPT_SGD;
+    const int64_t i4 = ((int64_t)blockIdx.x * 256 + threadIdx.x) * 4;
+    if (i4 >= n) return;
+    OptC c;
+    c.lr = a.lr; c.wd = a.wd;
+    int64_t end = n;
+    if (a.seg) {
+        const int64_t base = (int64_t)blockIdx.x * 1024;
+        int lo = 0, hi = a.nseg;
+        while (lo < hi) {
+            const int mid = (lo + hi) >> 1;
+            if (a.seg[mid].end > base) hi = mid; else lo = mid + 1;
+        }
+        while (lo < a.nseg && a.seg[lo].end <= i4) ++lo;
+        if (lo == a.nseg) return;
+        const maed_opt_segment sg = a.seg[lo];
+        if (sg.begin > i4) return;
+        end = sg.end < n ? sg.end : n;
+        c.lr = sg.lr; c.wd = sg.weight_decay;
+    }
+    float bc1 = a.bc1, bc2 = a.bc2;
+    if (a.st) { c.lr = a.st->lr; bc1 = a.st->bias_corr1; bc2 = a.st->bias_corr2; }
+    c.gs = a.clip ? a.gscale * a.clip->coef : a.gscale;
+    c.b1 = a.b1; c.b2 = a.b2; c.eps = a.eps; c.momentum = a.momentum; c.nesterov = a.nesterov;
+    c.step = ADAMS ? c.lr / bc1 : 0.f;
+    c.rbc2 = ADAMS ? rsqrtf(bc2) : 0.f;
+    c.decay = 1.f - c.lr * c.wd;
+    if (i4 + 4 <= end) {
+        float pp[4], gg[4], mm[4] = {0.f, 0.f, 0.f, 0.f}, vv[4] = {0.f, 0.f, 0.f, 0.f};
+        ld4(p + i4, pp); ld4(g + i4, gg);
+        if (ADAMS || MOM) ld4(m + i4, mm);
+        if (ADAMS) ld4(v + i4, vv);
+#pragma unroll
+        for (int j = 0; j < 4; ++j) opt_update<KIND, MOM>(pp[j], gg[j], mm[j], vv[j], c);
+        st4(p + i4, pp);
+        if (ADAMS || MOM) st4(m + i4, mm);
+        if (ADAMS) st4(v + i4, vv);
+        if (shadow) st4(shadow + i4, pp);
+    } else {
+        for (int64_t i = i4; i < end; ++i) {
+            float pi = p[i], mi = (ADAMS || MOM) ? m[i] : 0.f, vi = ADAMS ? v[i] : 0.f;
+            opt_update<KIND, MOM>(pi, g[i], mi, vi, c);
+            p[i] = pi;
+            if (ADAMS || MOM) m[i] = mi;
+            if (ADAMS) v[i] = vi;
+            if (shadow) shadow[i].v = f2bf(pi);
+        }
+    }
+}
+
+extern "C" int maed_opt_step(float* p, const float* g, float* m, float* v, void* shadow_bf16, int64_t n, const maed_opt_args* a, void* stream) {
+    MAED_CHECK_ARG(p && g && a && n >= 0, MAED_ERR_ARG, "opt_step: null pointer or negative size");
+    MAED_CHECK_ARG(a->kind == MAED_OPT_ADAM || a->kind == MAED_OPT_ADAMW || a->kind == MAED_OPT_SGD, MAED_ERR_ARG, "opt_step: unknown kind %d", a->kind);
+    const bool adams = a->kind != MAED_OPT_SGD, mom = !adams && a->momentum != 0.f;
+    MAED_CHECK_ARG(!adams || (m && v), MAED_ERR_ARG, "opt_step: Adam / AdamW need both moment arenas");
+    MAED_CHECK_ARG(!mom || m, MAED_ERR_ARG, "opt_step: SGD with momentum needs the buffer arena");
+    MAED_CHECK_ARG(a->n_segments >= 0 && (a->segments || a->n_segments == 0), MAED_ERR_ARG, "opt_step: %d segments without a table", a->n_segments);
+    MAED_CHECK_ARG(is_aligned(p, 16) && is_aligned(g, 16) && (!(adams || mom) || is_aligned(m, 16)) && (!adams || is_aligned(v, 16)) &&
+                   (!shadow_bf16 || is_aligned(shadow_bf16, 8)) && is_aligned(a->state, 8) && is_aligned(a->clip, 4) && is_aligned(a->segments, 8),
+                   MAED_ERR_ALIGN, "opt_step: arenas must be 16-B aligned, the state and the segment table 8-B");
+    if (n == 0 || (a->segments && a->n_segments == 0)) return MAED_OK;
+    OptK k;
+    k.lr = a->lr; k.b1 = a->beta1; k.b2 = a->beta2; k.eps = a->eps; k.wd = a->weight_decay; k.bc1 = a->bias_corr1; k.bc2 = a->bias_corr2;
+    k.momentum = a->momentum; k.nesterov = a->nesterov; k.gscale = a->gscale;
+    k.st = a->state; k.clip = a->clip; k.seg = a->segments; k.nseg = a->n_segments;
+    const int64_t nthr = (n + 3) / 4;
+    const dim3 grid((unsigned)((nthr + 255) / 256)), block(256);
+    bf16* sh = (bf16*)shadow_bf16;
+    if (a->kind == MAED_OPT_ADAM) hipLaunchKernelGGL((opt_kernel<MAED_OPT_ADAM, true>), grid, block, 0, (hipStream_t)stream, p, g, m, v, sh, n, k);
+    else if (a->kind == MAED_OPT_ADAMW) hipLaunchKernelGGL((opt_kernel<MAED_OPT_ADAMW, true>), grid, block, 0, (hipStream_t)stream, p, g, m, v, sh, n, k);
+    else if (mom) hipLaunchKernelGGL((opt_kernel<MAED_OPT_SGD, true>), grid, block, 0, (hipStream_t)stream, p, g, m, v, sh, n, k);
+    else hipLaunchKernelGGL((opt_kernel<MAED_OPT_SGD, false>), grid, block, 0, (hipStream_t)stream, p, g, m, v, sh, n, k);
+    MAED_CHECK_LAUNCH("opt_step");
+    return MAED_OK;
+}

@@ -268,16 +268,11 @@ class GradBucketer:
             ops.bump_weight_epoch()
 
 
-class FusedAdam(torch.optim.Optimizer):
-    """torch.optim.Adam semantics (L2 weight decay) as ONE kernel over the arena (maed_adam_step).
+class _ArenaOptimizer(torch.optim.Optimizer):
+    """What FusedAdam and FusedSGD share: one parameter group per tensor in named_parameters() order, the bucketer protocol (finish / unmarked / consumed, 1/world),
+    the global-norm clip on the device (maed_grad_norm) and the segment table of maed_opt_step (docs/design/15_optimizers.md)."""
 
-    Drop-in for the optimizer `lib/utils/utils.py:127-132` builds: a torch.optim.Optimizer with one parameter group per
-    tensor in `model.named_parameters()` order (pass `model`), so `LambdaLR` (train.py:123-127) drives `param_groups[*]['lr']`
-    and `state_dict()` / `load_state_dict()` speak torch.optim.Adam's format -- the 'optimizer' entry of the reference's
-    `epoch_N.pth.tar` checkpoints (trainer.py:330-368) resumes here and vice versa.  Compute-dtype weight copies are
-    rebuilt lazily by the modules after a step (ops.WEIGHT_EPOCH)."""
-
-    def __init__(self, arena, lr=1e-4, betas=(0.9, 0.999), eps=1e-8, weight_decay=0.0, bucketer=None, model=None):
+    def _setup(self, arena, defaults, bucketer, model, max_grad_norm):
         self.arena, self.bucketer = arena, bucketer
         order = list(getattr(arena, "definition_order", range(len(arena.params))))     # named_parameters() order even without model=
         if model is not None:   # the reference's group order = named_parameters() order (the arena is in forward order)
@@ -285,12 +280,87 @@ class FusedAdam(torch.optim.Optimizer):
             assert len(order) == len(arena.params)
         self._order = order
         groups = [{"params": [arena.params[i]], "name": arena.names[i]} for i in order]
-        super().__init__(groups, dict(lr=lr, betas=betas, eps=eps, weight_decay=weight_decay, amsgrad=False))
+        torch.optim.Optimizer.__init__(self, groups, defaults)
+        self.step_count = 0
+        self.device_state = None    # ops.DeviceTrainState: lr and bias corrections are then read from device memory (graphed.GraphedTrainStep; FusedAdam's default rule, uniform groups)
+        self._stepped = set()       # arena indices that have received at least one update (torch's optimizers keep no state for the others)
+        if max_grad_norm is not None and not max_grad_norm > 0:
+            raise ValueError("max_grad_norm must be positive (None: no clipping)")
+        self.max_grad_norm = max_grad_norm
+        self._clip = ops.clip_record(arena.flat.device) if max_grad_norm is not None else None      # maed_clip_state, written by every step
+        self._partials = None
+
+    # clip_grad_norm_'s return value and the non-finite flag of the last step, as views of the device record: `.tolist()` them with the loss terms, no copy is made here
+    grad_norm = property(lambda self: None if self._clip is None else self._clip[1])
+    grad_nonfinite = property(lambda self: None if self._clip is None else self._clip.view(torch.int32)[3])
+
+    def zero_grad(self, set_to_none=False):
+        self.arena.zero_grad()
+
+    def _begin_step(self):
+        """-> (world, arena indices without a gradient this step).  torch's optimizers skip parameters whose .grad is None (ts_attn in the non-parallel st_modes, any
+        unused parameter): no moment decay, no weight decay.  The arena's gradients are never None, so "received no gradient" comes from the bucketer's reports."""
+        world, skip = 1, set()
+        if self.bucketer is not None:
+            self.bucketer.finish()
+            world = self.bucketer.world
+            skip = set(self.bucketer.unmarked)
+            self.bucketer.consumed()
+        self.step_count += 1
+        self._stepped.update(i for i in range(len(self.arena.params)) if i not in skip)
+        return world, skip
+
+    def _clip_norm(self, world):
+        """the norm of the REDUCED gradients (the bucketer has finished) with the 1/world scale, into the device record; skipped tensors and padding are zero"""
+        if self._clip is None:
+            return None
+        if self._partials is None:
+            self._partials = torch.empty(ops.grad_norm_partials(), dtype=torch.float32, device=self.arena.flat.device)
+        ops.grad_norm(self.arena.grad, 1.0 / world, self.max_grad_norm, self._partials, self._clip)
+        return self._clip
+
+    def _segment_launches(self, skip, key_of):
+        """[(group, [(begin, end, lr, weight_decay), ...])]: one launch per distinct key_of(group) (the scalars a segment does not carry: normally one), the active
+        tensors in arena order, neighbours with equal lr / weight_decay merged (the padding between them is zero in every arena)"""
+        a, group_of = self.arena, dict(zip(self._order, self.param_groups))
+        launches = {}
+        prev = None        # key of the previous tensor in arena order, None when that one is skipped
+        for i in range(len(a.params)):
+            if i in skip:
+                prev = None
+                continue
+            g = group_of[i]
+            k = key_of(g)
+            lr, wd = g["lr"], g["weight_decay"]
+            o, e = a.offsets[i], a.offsets[i] + a.params[i].numel()
+            segs = launches.setdefault(k, (g, []))[1]
+            if prev == k and segs and (segs[-1][2], segs[-1][3]) == (lr, wd):
+                segs[-1] = (segs[-1][0], e, lr, wd)
+            else:
+                segs.append((o, e, lr, wd))
+            prev = k
+        return list(launches.values())
+
+
+class FusedAdam(_ArenaOptimizer):
+    """torch.optim.Adam semantics (L2 weight decay) as ONE kernel over the arena (maed_adam_step).
+
+    Drop-in for the optimizer `lib/utils/utils.py:127-132` builds: a torch.optim.Optimizer with one parameter group per
+    tensor in `model.named_parameters()` order (pass `model`), so `LambdaLR` (train.py:123-127) drives `param_groups[*]['lr']`
+    and `state_dict()` / `load_state_dict()` speak torch.optim.Adam's format -- the 'optimizer' entry of the reference's
+    `epoch_N.pth.tar` checkpoints (trainer.py:330-368) resumes here and vice versa.  Compute-dtype weight copies are
+    rebuilt lazily by the modules after a step (ops.WEIGHT_EPOCH).
+
+    decoupled_weight_decay=True (the name FusedAdamW): torch.optim.AdamW's rule, p *= 1 - lr*wd in front of the update, state interchangeable with AdamW's.
+    max_grad_norm=x: the gradients are clipped to global L2 norm x as torch.nn.utils.clip_grad_norm_ does, on the device (`grad_norm`, `grad_nonfinite`).
+    Either of them, or parameter groups that differ (see no_decay_groups), takes maed_opt_step: one launch for every group through a segment table."""
+
+    def __init__(self, arena, lr=1e-4, betas=(0.9, 0.999), eps=1e-8, weight_decay=0.0, bucketer=None, model=None, decoupled_weight_decay=False, max_grad_norm=None):
+        self.decoupled = bool(decoupled_weight_decay)
+        self._setup(arena, dict(lr=lr, betas=betas, eps=eps, weight_decay=weight_decay, amsgrad=False, decoupled_weight_decay=self.decoupled), bucketer, model,
+                    max_grad_norm)
         self.exp_avg = torch.zeros_like(arena.flat)
         self.exp_avg_sq = torch.zeros_like(arena.flat)
-        self.step_count = 0
-        self.device_state = None    # ops.DeviceTrainState: lr and bias corrections are then read from device memory (graphed.GraphedTrainStep; uniform groups only)
-        self._stepped = set()       # arena indices that have received at least one update (torch.optim.Adam keeps no state for the others)
 
     # kept as attributes for callers that read them
     lr = property(lambda self: self.param_groups[0]["lr"])
@@ -298,29 +368,34 @@ class FusedAdam(torch.optim.Optimizer):
     eps = property(lambda self: self.param_groups[0]["eps"])
     weight_decay = property(lambda self: self.param_groups[0]["weight_decay"])
 
-    def zero_grad(self, set_to_none=False):
-        self.arena.zero_grad()
-
     def _uniform(self):
         g0 = self.param_groups[0]
         key = (g0["lr"], tuple(g0["betas"]), g0["eps"], g0["weight_decay"])
         return all((g["lr"], tuple(g["betas"]), g["eps"], g["weight_decay"]) == key for g in self.param_groups)
 
+    def _step_segments(self, world, skip, clip, uniform):
+        """maed_opt_step: every group in one launch (per distinct betas / eps)"""
+        a = self.arena
+        kind = L.OPT_ADAMW if self.decoupled else L.OPT_ADAM
+        for g, segs in self._segment_launches(skip, lambda g: (tuple(g["betas"]), g["eps"])):
+            whole = uniform and not skip      # nothing to tell apart: no table
+            tab = None if whole else ops.opt_segments(segs, a.flat.device)
+            ops.opt_step(kind, a.flat, a.grad, self.exp_avg, self.exp_avg_sq, None, lr=g["lr"], beta1=g["betas"][0], beta2=g["betas"][1], eps=g["eps"],
+                         wd=g["weight_decay"], step=self.step_count, gscale=1.0 / world, clip=clip, segments=tab, n_segments=0 if whole else len(segs))
+
     @torch.no_grad()
     def step(self, closure=None):
-        world = 1
-        if self.bucketer is not None:
-            self.bucketer.finish()
-            world = self.bucketer.world
-        self.step_count += 1
+        world, skip = self._begin_step()
         a = self.arena
-        # torch.optim.Adam skips parameters whose .grad is None (ts_attn in the non-parallel st_modes, any unused parameter): no moment decay, no weight
-        # decay.  The arena's gradients are never None, so "received no gradient this step" comes from the bucketer's readiness reports.
-        skip = set(self.bucketer.unmarked) if self.bucketer is not None else set()
-        if self.bucketer is not None:
-            self.bucketer.consumed()
-        self._stepped.update(i for i in range(len(a.params)) if i not in skip)
-        if self._uniform():     # the reference's case: every group shares the schedule -> one launch over the whole arena (or per run of active tensors)
+        uniform = self._uniform()
+        if self.device_state is not None and not uniform:
+            raise RuntimeError("FusedAdam.device_state needs one schedule for every parameter group (the reference's case)")
+        if self.device_state is not None and (self._clip is not None or self.decoupled):
+            raise RuntimeError("FusedAdam.device_state (graphed.GraphedTrainStep) serves the default rule only: no max_grad_norm, no decoupled_weight_decay")
+        clip = self._clip_norm(world)
+        if clip is not None or self.decoupled or not uniform:
+            self._step_segments(world, skip, clip, uniform)
+        else:                   # the reference's case: every group shares the schedule -> one launch over the whole arena (or per run of active tensors)
             g = self.param_groups[0]
             runs = [(0, a.numel)]
             if skip:
@@ -347,15 +422,6 @@ class FusedAdam(torch.optim.Optimizer):
                 else:
                     ops.adam_step(a.flat[lo:hi], a.grad[lo:hi], self.exp_avg[lo:hi], self.exp_avg_sq[lo:hi], None, g["lr"], g["betas"][0], g["betas"][1], g["eps"],
                                   g["weight_decay"], self.step_count, gscale=1.0 / world)
-        else:                   # per-group hyper-parameters: one launch per tensor
-            if self.device_state is not None:
-                raise RuntimeError("FusedAdam.device_state needs one schedule for every parameter group (the reference's case)")
-            for g, i in zip(self.param_groups, self._order):
-                if i in skip:
-                    continue
-                o, n = a.offsets[i], a.params[i].numel()
-                ops.adam_step(a.flat[o:o + n], a.grad[o:o + n], self.exp_avg[o:o + n], self.exp_avg_sq[o:o + n], None, g["lr"],
-                              g["betas"][0], g["betas"][1], g["eps"], g["weight_decay"], self.step_count, gscale=1.0 / world)
         ops.bump_weight_epoch()
 
     # ---- torch.optim.Adam-compatible (de)serialisation ------------------------------------------------------------
@@ -393,3 +459,103 @@ class FusedAdam(torch.optim.Optimizer):
             assert len(set(steps)) == 1, "per-tensor step counts differ: not an Adam state this optimizer can represent"
             self.step_count = steps[0]
         self.state.clear()
+        for g in self.param_groups:         # the rule is this optimizer's, whichever of Adam / AdamW wrote the checkpoint
+            g["decoupled_weight_decay"] = self.decoupled
+
+
+class FusedAdamW(FusedAdam):
+    """torch.optim.AdamW (decoupled weight decay, default 1e-2) over the arena: FusedAdam(decoupled_weight_decay=True)"""
+
+    def __init__(self, arena, lr=1e-3, betas=(0.9, 0.999), eps=1e-8, weight_decay=1e-2, bucketer=None, model=None, max_grad_norm=None):
+        super().__init__(arena, lr=lr, betas=betas, eps=eps, weight_decay=weight_decay, bucketer=bucketer, model=model, decoupled_weight_decay=True,
+                         max_grad_norm=max_grad_norm)
+
+
+class FusedSGD(_ArenaOptimizer):
+    """torch.optim.SGD (dampening 0) as one kernel over the arena (maed_opt_step, MAED_OPT_SGD): the optimizer `lib/utils/utils.py:121-126` builds for
+    TRAIN.OPTIM: sgd.  One group per tensor in named_parameters() order, the bucketer protocol and the weight-epoch bump of FusedAdam; state_dict() /
+    load_state_dict() speak torch.optim.SGD's format (`momentum_buffer`; none for momentum 0 and for tensors that never stepped).  A zero-initialised buffer makes
+    the first step copy the gradient, as torch's does."""
+
+    def __init__(self, arena, lr, momentum=0.0, weight_decay=0.0, nesterov=False, bucketer=None, model=None, max_grad_norm=None, dampening=0.0):
+        if dampening != 0:
+            raise ValueError("FusedSGD: dampening must be 0 (the kernel has no first-step flag)")
+        if nesterov and momentum <= 0:
+            raise ValueError("Nesterov momentum requires a momentum and zero dampening")      # torch.optim.SGD's own check
+        self._setup(arena, dict(lr=lr, momentum=momentum, dampening=0.0, weight_decay=weight_decay, nesterov=bool(nesterov), maximize=False, foreach=None,
+                                differentiable=False, fused=None), bucketer, model, max_grad_norm)
+        self.momentum_buffer = torch.zeros_like(arena.flat) if momentum != 0 else None
+
+    lr = property(lambda self: self.param_groups[0]["lr"])
+    momentum = property(lambda self: self.param_groups[0]["momentum"])
+    weight_decay = property(lambda self: self.param_groups[0]["weight_decay"])
+
+    def _uniform(self):
+        key = lambda g: (g["lr"], g["momentum"], g["nesterov"], g["weight_decay"])
+        k0 = key(self.param_groups[0])
+        return all(key(g) == k0 for g in self.param_groups)
+
+    @torch.no_grad()
+    def step(self, closure=None):
+        world, skip = self._begin_step()
+        a = self.arena
+        if self.device_state is not None:
+            raise RuntimeError("FusedSGD does not run under a device record (graphed.GraphedTrainStep captures the default FusedAdam step only)")
+        clip = self._clip_norm(world)
+        uniform = self._uniform()
+        if any(g.get("dampening", 0) != 0 for g in self.param_groups):
+            raise ValueError("FusedSGD: dampening must be 0")
+        if self.momentum_buffer is None and any(g["momentum"] != 0 for g in self.param_groups):
+            self.momentum_buffer = torch.zeros_like(a.flat)
+        for g, segs in self._segment_launches(skip, lambda g: (g["momentum"], bool(g["nesterov"]))):
+            whole = uniform and not skip
+            tab = None if whole else ops.opt_segments(segs, a.flat.device)
+            ops.opt_step(L.OPT_SGD, a.flat, a.grad, self.momentum_buffer, None, None, lr=g["lr"], wd=g["weight_decay"], momentum=g["momentum"],
+                         nesterov=g["nesterov"], gscale=1.0 / world, clip=clip, segments=tab, n_segments=0 if whole else len(segs))
+        ops.bump_weight_epoch()
+
+    # ---- torch.optim.SGD-compatible (de)serialisation -------------------------------------------------------------
+    def _view(self, i):
+        o, p = self.arena.offsets[i], self.arena.params[i]
+        return self.momentum_buffer[o:o + p.numel()].view(p.shape)
+
+    def state_dict(self):
+        group_of = dict(zip(self._order, self.param_groups))
+        if self.momentum_buffer is not None:
+            for i in self._order:
+                if i in self._stepped and group_of[i]["momentum"] != 0:      # torch.optim.SGD: no buffer without momentum, no state before the first gradient
+                    self.state[self.arena.params[i]] = {"momentum_buffer": self._view(i).clone()}
+        try:
+            return super().state_dict()
+        finally:
+            self.state.clear()
+
+    def load_state_dict(self, state_dict):
+        super().load_state_dict(state_dict)     # validates group structure, casts state to the parameters' device/dtype
+        for i in self._order:
+            st = self.state.get(self.arena.params[i])
+            if not st or st.get("momentum_buffer") is None:
+                continue
+            if self.momentum_buffer is None:
+                self.momentum_buffer = torch.zeros_like(self.arena.flat)
+            self._view(i).copy_(st["momentum_buffer"])
+            self._stepped.add(i)
+        self.state.clear()
+
+
+def no_decay_groups(optimizer, model):
+    """The timm convention for decoupled decay, opt-in: weight_decay = 0 on the groups `model.no_weight_decay()` names (any module of the model may declare it; the
+    names are relative to that module) and on every 1-D parameter (biases, norm scales).  Returns the names changed.  The groups then differ, which FusedAdam /
+    FusedSGD serve with one segment launch."""
+    skip = set()
+    for prefix, m in model.named_modules():
+        fn = getattr(m, "no_weight_decay", None)
+        if callable(fn):
+            skip.update((prefix + "." if prefix else "") + n for n in fn())
+    changed = []
+    for g in optimizer.param_groups:
+        p = g["params"][0]
+        if g.get("name") in skip or p.ndim <= 1:
+            g["weight_decay"] = 0.0
+            changed.append(g.get("name"))
+    return changed

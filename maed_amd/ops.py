@@ -607,6 +607,43 @@ def adam_step_dev(p, g, m, v, shadow, state, beta1, beta2, eps, wd, gscale=1.0):
     check(L.lib().maed_adam_step_dev(_p(p), _p(g), _p(m), _p(v), _p(shadow), p.numel(), _p(state), beta1, beta2, eps, wd, gscale, _stream()), "adam_step_dev")
 
 
+_SEG_DTYPE = _np.dtype([("begin", "i8"), ("end", "i8"), ("lr", "f4"), ("weight_decay", "f4")])     # maed_opt_segment
+
+
+def grad_norm_partials():
+    """floats of workspace maed_grad_norm needs (a constant of the library)"""
+    return int(L.lib().maed_grad_norm_partials())
+
+
+def clip_record(device):
+    """a zeroed maed_clip_state {sqnorm, norm, coef, nonfinite} as 4 fp32 words on `device` (view word 3 as int32 for the flag)"""
+    return torch.zeros(4, dtype=torch.float32, device=device)
+
+
+def grad_norm(g, gscale, max_norm, partials, record):
+    """record <- {sum((gscale*g)^2), its root, clip_grad_norm_'s coefficient for max_norm (<= 0 or None: 1), non-finite flag}: two launches in a fixed order,
+    nothing returns to the host"""
+    assert g.dtype == torch.float32 and g.is_contiguous() and partials.numel() >= grad_norm_partials() and record.numel() * record.element_size() >= 16
+    check(L.lib().maed_grad_norm(_p(g), g.numel(), gscale, float(max_norm or 0.0), _p(partials), _p(record), _stream()), "grad_norm")
+
+
+def opt_segments(entries, device):
+    """[(begin, end, lr, weight_decay), ...] (sorted by begin, disjoint, begin % 4 == 0) -> device table of maed_opt_segment; equal tables share one upload"""
+    tab = _np.zeros(len(entries), dtype=_SEG_DTYPE)
+    for k, e in enumerate(entries):
+        tab[k] = e
+    return _upload_table(tab, device)
+
+
+def opt_step(kind, p, g, m, v, shadow, lr=0.0, beta1=0.9, beta2=0.999, eps=1e-8, wd=0.0, step=1, momentum=0.0, nesterov=False, gscale=1.0, state=None, clip=None,
+             segments=None, n_segments=0):
+    """maed_opt_step: kind L.OPT_ADAM / OPT_ADAMW / OPT_SGD over flat fp32 arenas; `state` (DeviceTrainState.dev), `clip` (a grad_norm record) and `segments`
+    (opt_segments) are device tensors read when the kernel runs"""
+    a = L.OptArgs(kind, lr, beta1, beta2, eps, wd, 1.0 - beta1 ** step, 1.0 - beta2 ** step, momentum, int(bool(nesterov)), gscale, _p(state), _p(clip),
+                  _p(segments), n_segments)
+    check(L.lib().maed_opt_step(_p(p), _p(g), _p(m), _p(v), _p(shadow), p.numel(), C.byref(a), _stream()), "opt_step")
+
+
 class DeviceTrainState:
     """include/maed_hip.h `maed_train_state`: the per-step scalars of a training step (learning rate, Adam's bias corrections, the Dropout seed) in a 32-byte
     device record, so that the launches of a step carry no argument that changes from step to step -- the precondition of replaying the step as a hipGraph

@@ -45,6 +45,17 @@ class TrainStep:
         return total, terms
 
 
+def get_optimizer(arena, optim_type, lr, weight_decay, momentum, bucketer=None, model=None, **kw):
+    """lib/utils/utils.py:120-135 over a ParamArena: the same spellings, the SGD branch ignores weight_decay as the reference's does (torch.optim.SGD's default 0),
+    the Adam branch ignores momentum, anything else raises ModuleNotFoundError.  **kw reaches the optimizer (max_grad_norm=..., nesterov=...)."""
+    from .ddp import FusedAdam, FusedSGD
+    if optim_type in ['sgd', 'SGD']:
+        return FusedSGD(arena, lr=lr, momentum=momentum, bucketer=bucketer, model=model, **kw)
+    if optim_type in ['Adam', 'adam', 'ADAM']:
+        return FusedAdam(arena, lr=lr, weight_decay=weight_decay, bucketer=bucketer, model=model, **kw)
+    raise ModuleNotFoundError
+
+
 def save_checkpoint(path, model, optimizer, epoch, performance, ddp_prefix=True):
     """trainer.py:330-352: {'epoch', 'state_dict', 'performance', 'optimizer'}; the reference saves the DDP-wrapped model, so
     its keys carry a 'module.' prefix (eval.py:29 strips it) -- kept by default for interchangeability"""

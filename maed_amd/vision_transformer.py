@@ -329,6 +329,10 @@ class VisionTransformer(nn.Module):
             nn.init.constant_(m.bias, 0)
             nn.init.constant_(m.weight, 1.0)
 
+    @torch.jit.ignore
+    def no_weight_decay(self):  # vision_transformer.py:378-379 (the timm convention: ddp.no_decay_groups)
+        return {'pos_embed', 'cls_token'}
+
     def forward_tokens(self, x, seqlen=1):
         """everything up to (and including) the last Block: (F,3,S,S) -> fp32 tokens (F,P,C)"""
         patch = self.patch_embed(x)
