@@ -676,6 +676,8 @@ int maed_comm_load(const char* librccl_path);
 int maed_comm_unique_id(void* id128);
 int maed_comm_init(int rank, int world, const void* unique_id);
 int maed_comm_allreduce_async(void* buf, size_t n, int dtype, void* compute_stream);
+/* allreduce_f64_async: the same for n doubles (the records of the cross-rank BatchNorm statistics). */
+int maed_comm_allreduce_f64_async(double* buf, size_t n, void* compute_stream);
 int maed_comm_wait(void* compute_stream);
 int maed_comm_world(void);
 int maed_comm_destroy(void);
@@ -820,6 +822,23 @@ int maed_batchnorm_bwd_reduce(const void* x, const void* dy, const uint8_t* relu
                               const float* beta, double* partials, float* sums, float* dgamma, float* dbeta, int64_t M, int C, int relu, int dtype, void* stream);
 int maed_batchnorm_bwd_apply(const void* x, const void* dy, const uint8_t* relu_mask, const float* mean, const float* mean_lo, const float* rstd, const float* gamma,
                              const float* beta, const float* sums, void* dx, void* dres, int64_t M, int C, int relu, int dtype, void* stream);
+/* Statistics over the batch of all ranks (SyncBatchNorm): the same passes with an all-reduce(SUM) of an fp64 record between the reduction and its consumer; the
+ * caller issues the all-reduce (maed_comm_allreduce_f64_async, or any other sum over ranks).  Ranks may hold different numbers of rows (each at least one), so the
+ * global row count travels in the record and is read on the device.
+ * maed_batchnorm_stats_local: the statistics pass of maed_batchnorm_stats, not finalized: record (2 * C + 1 doubles) = (sum x, sum x^2) per channel -- the chunk
+ *   partials added in maed_batchnorm_finalize's order -- followed by M.
+ * maed_batchnorm_finalize_dev: maed_batchnorm_finalize's arithmetic on a (reduced) record, count = record[2 * C].
+ * maed_batchnorm_bwd_reduce_local: maed_batchnorm_bwd_reduce with record (2 * C doubles) = (sum dy', sum dy' xhat) per channel in place of the fp32 sums;
+ *   dgamma / dbeta accumulate this rank's sums (the gradient all-reduce adds the ranks).
+ * maed_batchnorm_bwd_apply_dev: maed_batchnorm_bwd_apply with the sums from a (reduced) backward record and the row count from count[0] (device memory: the
+ *   forward record's last slot).  A record that was not reduced gives the results of the one-rank entry points bit for bit. */
+int maed_batchnorm_stats_local(const void* x, int64_t M, int C, int dtype, double* partials, double* record, void* stream);
+int maed_batchnorm_finalize_dev(const double* record, int C, float eps, float* mean, float* mean_lo, float* rstd, float* running_mean, float* running_var,
+                                float momentum, void* stream);
+int maed_batchnorm_bwd_reduce_local(const void* x, const void* dy, const uint8_t* relu_mask, const float* mean, const float* mean_lo, const float* rstd, const float* gamma,
+                                    const float* beta, double* partials, double* record, float* dgamma, float* dbeta, int64_t M, int C, int relu, int dtype, void* stream);
+int maed_batchnorm_bwd_apply_dev(const void* x, const void* dy, const uint8_t* relu_mask, const float* mean, const float* mean_lo, const float* rstd, const float* gamma,
+                                 const float* beta, const double* record, const double* count, void* dx, void* dres, int64_t M, int C, int relu, int dtype, void* stream);
 /* MaxPool2d(kernel 3, stride 2, padding 1 with -inf) on channels_last x (N,H,W,C), C % 8 == 0: y (N, (H-1)/2+1, (W-1)/2+1, C) and the winning tap per output
  * element (idx, uint8, same shape as y; ATen tie / NaN rule, as maed_maxpool3s2_same_*); backward gathers dx. */
 int maed_maxpool3s2p1_fwd(const void* x, void* y, uint8_t* idx, int N, int H, int W, int C, int dtype, void* stream);

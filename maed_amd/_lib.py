@@ -163,6 +163,7 @@ SIGNATURES = {
     "maed_comm_unique_id": (i32, [vp]),
     "maed_comm_init": (i32, [i32, i32, vp]),
     "maed_comm_allreduce_async": (i32, [vp, C.c_size_t, i32, vp]),
+    "maed_comm_allreduce_f64_async": (i32, [vp, C.c_size_t, vp]),
     "maed_comm_wait": (i32, [vp]),
     "maed_comm_world": (i32, []),
     "maed_comm_destroy": (i32, []),
@@ -208,6 +209,10 @@ SIGNATURES = {
     "maed_batchnorm_apply_fwd": (i32, [vp, vp, vp, vp, vp, vp, vp, vp, i64, i32, i32, i32, vp]),
     "maed_batchnorm_bwd_reduce": (i32, [vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, i64, i32, i32, i32, vp]),
     "maed_batchnorm_bwd_apply": (i32, [vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, i64, i32, i32, i32, vp]),
+    "maed_batchnorm_stats_local": (i32, [vp, i64, i32, i32, vp, vp, vp]),
+    "maed_batchnorm_finalize_dev": (i32, [vp, i32, f32, vp, vp, vp, vp, vp, f32, vp]),
+    "maed_batchnorm_bwd_reduce_local": (i32, [vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, i64, i32, i32, i32, vp]),
+    "maed_batchnorm_bwd_apply_dev": (i32, [vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, i64, i32, i32, i32, vp]),
     "maed_maxpool3s2p1_fwd": (i32, [vp, vp, vp, i32, i32, i32, i32, i32, vp]),
     "maed_maxpool3s2p1_bwd": (i32, [vp, vp, vp, i32, i32, i32, i32, i32, vp]),
     "maed_avgpool_fwd": (i32, [vp, vp, i32, i32, i32, i32, vp]),

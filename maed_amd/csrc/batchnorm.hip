@@ -322,6 +322,83 @@ __global__ __launch_bounds__(BN_NT) void bn_bwd_apply_kernel(const T* __restrict
     }
 }
 
+// ---- statistics over the batch of all ranks (maed_batchnorm_*_local / *_dev) ---------------------------------------------------------------------------------
+// Between the reduction and its consumer sits an all-reduce(SUM) of an fp64 record the host issues: forward record = (sum x, sum x^2) per channel followed by the
+// row count (2 C + 1 doubles; ranks may hold different numbers of rows, so the global count is device data and never visits the host), backward record =
+// (sum dy', sum dy' xhat) per channel (2 C doubles).  The chunk partials are added in bn_combine's order and the consumers repeat bn_finalize_kernel's /
+// bn_bwd_apply_kernel's arithmetic, so a record that was not reduced (one rank) gives the bits of the one-rank entry points.
+__global__ __launch_bounds__(BN_NT) void bn_record_kernel(const double* __restrict__ part, int chunks, int C, double* __restrict__ rec, double count,
+                                                          float* __restrict__ dgamma, float* __restrict__ dbeta) {
+    int c; double s, q;
+    if (!bn_combine(part, chunks, C, c, s, q)) return;
+    rec[2 * c] = s; rec[2 * c + 1] = q;
+    if (count > 0.0 && c == 0) rec[2 * (int64_t)C] = count;     // forward record only
+    if (dbeta) dbeta[c] += (float)s;
+    if (dgamma) dgamma[c] += (float)q;
+}
+
+__global__ __launch_bounds__(BN_NT) void bn_finalize_dev_kernel(const double* __restrict__ rec, int C, float eps, float* __restrict__ mean, float* __restrict__ mean_lo,
+                                                                float* __restrict__ rstd, float* __restrict__ rmean, float* __restrict__ rvar, float momentum) {
+    const int c = (int)blockIdx.x * BN_NT + (int)threadIdx.x;
+    if (c >= C) return;
+    const double s = rec[2 * c], q = rec[2 * c + 1], count = rec[2 * (int64_t)C];
+    const double m = s / count;
+    double var = q / count - m * m;          // biased
+    if (var < 0.0) var = 0.0;
+    mean[c] = (float)m;
+    if (mean_lo) mean_lo[c] = (float)(m - (double)(float)m);
+    rstd[c] = (float)(1.0 / sqrt(var + (double)eps));
+    if (rmean) rmean[c] = (float)((1.0 - (double)momentum) * (double)rmean[c] + (double)momentum * m);
+    if (rvar) {
+        const double unbiased = count > 1.0 ? var * (count / (count - 1.0)) : var;
+        rvar[c] = (float)((1.0 - (double)momentum) * (double)rvar[c] + (double)momentum * unbiased);
+    }
+}
+
+// bn_bwd_apply_kernel (not FROZEN) with the sums and the row count read from the reduced records
+template <typename T, int VEC, int MODE>
+__global__ __launch_bounds__(BN_NT) void bn_bwd_apply_dev_kernel(const T* __restrict__ x, const T* __restrict__ dy, const uint8_t* __restrict__ mask, const float* __restrict__ mean,
+                                                                 const float* __restrict__ mean_lo, const float* __restrict__ rstd, const float* __restrict__ gamma,
+                                                                 const float* __restrict__ beta, const double* __restrict__ sums, const double* __restrict__ count,
+                                                                 T* __restrict__ dx, T* __restrict__ dres, int M, int C, int rpc) {
+    const bn_lane l = bn_where<VEC>(M, C, rpc);
+    if (!l.active) return;
+    float mu[VEC], ml[VEC], rs[VEC], a[VEC], b[VEC], c1[VEC], c2[VEC];
+    {
+        float gg[VEC], bb[VEC];
+        bn_load_lo<VEC>(mean_lo, l.cg, ml);
+        ldv<VEC>(mean + l.cg * VEC, mu); ldv<VEC>(rstd + l.cg * VEC, rs); ldv<VEC>(gamma + l.cg * VEC, gg); ldv<VEC>(beta + l.cg * VEC, bb);
+        const float inv = 1.0f / (float)count[0];
+#pragma unroll
+        for (int j = 0; j < VEC; ++j) {
+            a[j] = rs[j] * gg[j]; b[j] = fmaf(-mu[j], a[j], bb[j]);
+            c1[j] = (float)sums[2 * (l.cg * VEC + j)] * inv;
+            c2[j] = (float)sums[2 * (l.cg * VEC + j) + 1] * inv;
+        }
+    }
+    const int64_t col = (int64_t)l.cg * VEC;
+    auto finish = [&](int r, const float (&v)[VEC], const float (&d)[VEC]) {
+        float o[VEC];
+#pragma unroll
+        for (int j = 0; j < VEC; ++j) o[j] = a[j] * ((d[j] - c1[j]) - ((v[j] - mu[j]) - ml[j]) * rs[j] * c2[j]);
+        stv<VEC>(dx + (int64_t)r * C + col, o);
+        if (dres) stv<VEC>(dres + (int64_t)r * C + col, d);
+    };
+    int r = l.r0 + l.rsub;
+    for (; r + 3 * l.rstep < l.r1; r += 4 * l.rstep) {
+        float v[4][VEC], d[4][VEC];
+#pragma unroll
+        for (int u = 0; u < 4; ++u) bn_dy_eff<T, VEC, MODE>(x, dy, mask, (int64_t)r + u * l.rstep, C, l.cg, a, b, v[u], d[u]);
+#pragma unroll
+        for (int u = 0; u < 4; ++u) finish(r + u * l.rstep, v[u], d[u]);
+    }
+    for (; r < l.r1; r += l.rstep) {
+        float v[VEC], d[VEC];
+        bn_dy_eff<T, VEC, MODE>(x, dy, mask, (int64_t)r, C, l.cg, a, b, v, d);
+        finish(r, v, d);
+    }
+}
+
 // ---- MaxPool2d(kernel 3, stride 2, padding 1) ------------------------------------------------------------------------------------------------------------
 // The structure of maed_maxpool3s2_same_* (backbone.hip) with symmetric padding: windows start at 2 * o - 1, Ho = (H - 1) / 2 + 1.  Ties / NaN follow ATen: the
 // first strictly greater value in (kh, kw) scan order wins, a NaN always wins.  A window always holds its centre tap (kh = kw = 1 is inside the image).
@@ -578,6 +655,85 @@ extern "C" int maed_batchnorm_bwd_apply(const void* x, const void* dy, const uin
 #undef BN_BAP_M
 #undef BN_BAP
     MAED_CHECK_LAUNCH("batchnorm_bwd_apply");
+    return MAED_OK;
+}
+
+// ---- the entry points with an all-reduce of a record between reduction and consumer (the one-rank entry points above stay as they are) ----
+extern "C" int maed_batchnorm_stats_local(const void* x, int64_t M, int C, int dtype, double* partials, double* record, void* stream) {
+    MAED_CHECK_ARG(x && partials && record, MAED_ERR_ARG, "batchnorm_stats_local: null pointer");
+    MAED_PROPAGATE(bn_check("batchnorm_stats_local", M, C));
+    MAED_CHECK_ARG(M >= 1, MAED_ERR_SHAPE, "batchnorm_stats_local: no rows");
+    MAED_CHECK_ARG(is_aligned(x, 16) && is_aligned(record, 8), MAED_ERR_ALIGN, "batchnorm_stats_local: x must be 16-B aligned, record 8-B");
+    hipStream_t s = (hipStream_t)stream;
+    if (dtype == MAED_BF16) {
+        const bn_geom g = bn_geometry(M, C, 8);
+        hipLaunchKernelGGL((bn_stats_kernel<bf16, 8>), dim3(g.chunks, g.ntile), dim3(BN_NT), 0, s, (const bf16*)x, partials, (int)M, C, g.rpc);
+    } else if (dtype == MAED_F32) {
+        const bn_geom g = bn_geometry(M, C, 4);
+        hipLaunchKernelGGL((bn_stats_kernel<float, 4>), dim3(g.chunks, g.ntile), dim3(BN_NT), 0, s, (const float*)x, partials, (int)M, C, g.rpc);
+    } else { maed_set_error("batchnorm_stats_local: bad dtype %d", dtype); return MAED_ERR_ARG; }
+    MAED_CHECK_LAUNCH("batchnorm_stats_local");
+    hipLaunchKernelGGL(bn_record_kernel, dim3((unsigned)((C + 15) / 16)), dim3(BN_NT), 0, s, (const double*)partials, bn_chunks(M), C, record, (double)M, (float*)nullptr,
+                       (float*)nullptr);
+    MAED_CHECK_LAUNCH("batchnorm_stats_local record");
+    return MAED_OK;
+}
+
+extern "C" int maed_batchnorm_finalize_dev(const double* record, int C, float eps, float* mean, float* mean_lo, float* rstd, float* running_mean, float* running_var,
+                                           float momentum, void* stream) {
+    MAED_CHECK_ARG(record && mean && rstd, MAED_ERR_ARG, "batchnorm_finalize_dev: null pointer");
+    MAED_CHECK_ARG(C > 0, MAED_ERR_SHAPE, "batchnorm_finalize_dev: C=%d", C);
+    MAED_CHECK_ARG(is_aligned(record, 8), MAED_ERR_ALIGN, "batchnorm_finalize_dev: record must be 8-B aligned");
+    hipLaunchKernelGGL(bn_finalize_dev_kernel, dim3((unsigned)((C + BN_NT - 1) / BN_NT)), dim3(BN_NT), 0, (hipStream_t)stream, record, C, eps, mean, mean_lo, rstd, running_mean,
+                       running_var, momentum);
+    MAED_CHECK_LAUNCH("batchnorm_finalize_dev");
+    return MAED_OK;
+}
+
+extern "C" int maed_batchnorm_bwd_reduce_local(const void* x, const void* dy, const uint8_t* relu_mask, const float* mean, const float* mean_lo, const float* rstd, const float* gamma,
+                                               const float* beta, double* partials, double* record, float* dgamma, float* dbeta, int64_t M, int C, int relu, int dtype, void* stream) {
+    MAED_CHECK_ARG(x && dy && mean && rstd && gamma && beta && partials && record, MAED_ERR_ARG, "batchnorm_bwd_reduce_local: null pointer");
+    MAED_PROPAGATE(bn_check("batchnorm_bwd_reduce_local", M, C));
+    MAED_CHECK_ARG(M >= 1, MAED_ERR_SHAPE, "batchnorm_bwd_reduce_local: no rows");
+    MAED_CHECK_ARG(is_aligned(x, 16) && is_aligned(dy, 16) && is_aligned(mean, 16) && is_aligned(mean_lo, 16) && is_aligned(rstd, 16) && is_aligned(gamma, 16) && is_aligned(beta, 16) &&
+                   is_aligned(record, 8), MAED_ERR_ALIGN, "batchnorm_bwd_reduce_local: 16-B alignment (record: 8-B)");
+    hipStream_t s = (hipStream_t)stream;
+    const int mode = bn_bwd_mode(relu, relu_mask);
+#define BN_RED(T_, V_, MODE_) do { const bn_geom g = bn_geometry(M, C, V_); \
+        hipLaunchKernelGGL((bn_bwd_reduce_kernel<T_, V_, MODE_>), dim3(g.chunks, g.ntile), dim3(BN_NT), 0, s, (const T_*)x, (const T_*)dy, relu_mask, mean, mean_lo, rstd, gamma, beta, \
+                           partials, (int)M, C, g.rpc); } while (0)
+#define BN_RED_T(T_, V_) do { if (mode == 2) BN_RED(T_, 8, 2); else if (mode == 1) BN_RED(T_, V_, 1); else BN_RED(T_, V_, 0); } while (0)
+    if (dtype == MAED_BF16) BN_RED_T(bf16, 8);
+    else if (dtype == MAED_F32) BN_RED_T(float, 4);
+    else { maed_set_error("batchnorm_bwd_reduce_local: bad dtype %d", dtype); return MAED_ERR_ARG; }
+#undef BN_RED_T
+#undef BN_RED
+    MAED_CHECK_LAUNCH("batchnorm_bwd_reduce_local");
+    hipLaunchKernelGGL(bn_record_kernel, dim3((unsigned)((C + 15) / 16)), dim3(BN_NT), 0, s, (const double*)partials, bn_chunks(M), C, record, 0.0, dgamma, dbeta);
+    MAED_CHECK_LAUNCH("batchnorm_bwd_reduce_local record");
+    return MAED_OK;
+}
+
+extern "C" int maed_batchnorm_bwd_apply_dev(const void* x, const void* dy, const uint8_t* relu_mask, const float* mean, const float* mean_lo, const float* rstd, const float* gamma,
+                                            const float* beta, const double* record, const double* count, void* dx, void* dres, int64_t M, int C, int relu, int dtype, void* stream) {
+    MAED_CHECK_ARG(x && dy && mean && rstd && gamma && beta && record && count && dx, MAED_ERR_ARG, "batchnorm_bwd_apply_dev: null pointer");
+    MAED_PROPAGATE(bn_check("batchnorm_bwd_apply_dev", M, C));
+    MAED_CHECK_ARG(is_aligned(x, 16) && is_aligned(dy, 16) && is_aligned(dx, 16) && is_aligned(dres, 16) && is_aligned(mean, 16) && is_aligned(mean_lo, 16) && is_aligned(rstd, 16) &&
+                   is_aligned(gamma, 16) && is_aligned(beta, 16) && is_aligned(record, 8) && is_aligned(count, 8), MAED_ERR_ALIGN,
+                   "batchnorm_bwd_apply_dev: 16-B alignment (record, count: 8-B)");
+    if (M == 0) return MAED_OK;
+    hipStream_t s = (hipStream_t)stream;
+    const int mode = bn_bwd_mode(relu, relu_mask);
+#define BN_BAP(T_, V_, MODE_) do { const bn_geom g = bn_geometry(M, C, V_); \
+        hipLaunchKernelGGL((bn_bwd_apply_dev_kernel<T_, V_, MODE_>), dim3(g.chunks, g.ntile), dim3(BN_NT), 0, s, (const T_*)x, (const T_*)dy, relu_mask, mean, mean_lo, rstd, gamma, beta, \
+                           record, count, (T_*)dx, (T_*)dres, (int)M, C, g.rpc); } while (0)
+#define BN_BAP_T(T_, V_) do { if (mode == 2) BN_BAP(T_, 8, 2); else if (mode == 1) BN_BAP(T_, V_, 1); else BN_BAP(T_, V_, 0); } while (0)
+    if (dtype == MAED_BF16) BN_BAP_T(bf16, 8);
+    else if (dtype == MAED_F32) BN_BAP_T(float, 4);
+    else { maed_set_error("batchnorm_bwd_apply_dev: bad dtype %d", dtype); return MAED_ERR_ARG; }
+#undef BN_BAP_T
+#undef BN_BAP
+    MAED_CHECK_LAUNCH("batchnorm_bwd_apply_dev");
     return MAED_OK;
 }
 

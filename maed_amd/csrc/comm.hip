@@ -85,6 +85,17 @@ extern "C" int maed_comm_allreduce_async(void* buf, size_t n, int dtype, void* c
     return MAED_OK;
 }
 
+// fp64 records of the cross-rank BatchNorm statistics (csrc/batchnorm.hip): the ordering protocol of maed_comm_allreduce_async, on the same side stream
+extern "C" int maed_comm_allreduce_f64_async(double* buf, size_t n, void* compute_stream) {
+    MAED_CHECK_ARG(g_comm, MAED_ERR_UNSUPPORTED, "comm_allreduce_f64: communicator not initialised");
+    MAED_CHECK_ARG(buf || n == 0, MAED_ERR_ARG, "comm_allreduce_f64: null buffer");
+    if (n == 0) return MAED_OK;
+    COMM_HIP(hipEventRecord(g_ev_ready, (hipStream_t)compute_stream), "comm_allreduce_f64: record");
+    COMM_HIP(hipStreamWaitEvent(g_side, g_ev_ready, 0), "comm_allreduce_f64: wait");
+    COMM_NCCL(g_api.AllReduce(buf, buf, n, ncclFloat64, ncclSum, g_comm, g_side), "ncclAllReduce");
+    return MAED_OK;
+}
+
 extern "C" int maed_comm_wait(void* compute_stream) {
     MAED_CHECK_ARG(g_comm, MAED_ERR_UNSUPPORTED, "comm_wait: communicator not initialised");
     COMM_HIP(hipEventRecord(g_ev_done, g_side), "comm_wait: record");

@@ -118,6 +118,11 @@ class RcclComm:
     def allreduce_async(self, t):
         L.check(L.lib().maed_comm_allreduce_async(ops._p(t), t.numel(), ops.dt_code(t.dtype), ops._stream()), "comm_allreduce_async")
 
+    def allreduce_f64_async(self, t):
+        """fp64 (the records of the cross-rank BatchNorm statistics, ops.StatSync); queues on the side stream behind the gradient buckets already issued"""
+        assert t.dtype == torch.float64
+        L.check(L.lib().maed_comm_allreduce_f64_async(ops._p(t), t.numel(), ops._stream()), "comm_allreduce_f64_async")
+
     def wait(self):
         L.check(L.lib().maed_comm_wait(ops._stream()), "comm_wait")
 

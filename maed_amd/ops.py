@@ -1876,6 +1876,102 @@ def batchnorm_bwd(x2, dy2, mean, rstd, gamma, beta, mask=None, relu=False, froze
     return dx, dres
 
 
+class StatSync:
+    """The cross-rank reducer of the BatchNorm statistics (resnet.convert_sync_batchnorm): all_reduce(t) sums a 1-D fp64 tensor in place over the ranks, ordered on
+    the current stream.  Built from a torch.distributed process group (None = the default group; gloo for host tensors, nccl on the device) or from a ddp.RcclComm
+    (the library's communicator: maed_comm_allreduce_f64_async + maed_comm_wait).  `active`: the norm layers issue collectives -- world > 1, or force_collectives on
+    a world of one (the plumbing on a single GPU, as GradBucketer's switch of that name)."""
+
+    def __init__(self, process_group=None, comm=None, force_collectives=False):
+        import torch.distributed as dist
+        self.pg, self.comm = process_group, comm
+        have_pg = dist.is_available() and dist.is_initialized()
+        self.world = comm.world if comm is not None else (dist.get_world_size(process_group) if have_pg else 1)
+        self.active = self.world > 1 or (force_collectives and (comm is not None or have_pg))
+
+    def all_reduce(self, t):
+        assert t.dtype == torch.float64 and t.dim() == 1 and t.is_contiguous()
+        if self.comm is not None:
+            self.comm.allreduce_f64_async(t)
+            self.comm.wait()
+        else:
+            import torch.distributed as dist
+            dist.all_reduce(t, group=self.pg)
+
+
+def batchnorm_stats_sync(x2, eps, sync, running_mean=None, running_var=None, momentum=0.1):
+    """batchnorm_stats over the rows of all ranks: this rank's (sum, sum of squares) per channel and its row count as one fp64 record (2 C + 1), summed over the
+    ranks by `sync`, then finalized on the device with the global count (it never visits the host: ranks may hold different numbers of rows).
+    Returns (mean, rstd, mean_lo, count): count is the record's last slot, a 1-element fp64 view the backward reads."""
+    M, C_ = x2.shape
+    rec = torch.empty(2 * C_ + 1, dtype=torch.float64, device=x2.device)
+    partials = batchnorm_scratch(M, C_, x2.device)
+    check(L.lib().maed_batchnorm_stats_local(_p(x2), M, C_, dt_code(x2.dtype), _p(partials), _p(rec), _stream()), "batchnorm_stats_local")
+    sync.all_reduce(rec)
+    stat = torch.empty(3, C_, dtype=torch.float32, device=x2.device)
+    mean, mean_lo, rstd = stat[0], stat[1], stat[2]
+    check(L.lib().maed_batchnorm_finalize_dev(_p(rec), C_, eps, _p(mean), _p(mean_lo), _p(rstd), _p(running_mean), _p(running_var), momentum, _stream()),
+          "batchnorm_finalize_dev")
+    return mean, rstd, mean_lo, rec[2 * C_:]
+
+
+def batchnorm_bwd_sync(x2, dy2, mean, rstd, gamma, beta, count, sync, mask=None, relu=False, dgamma=None, dbeta=None, want_dres=False, mean_lo=None):
+    """batchnorm_bwd for statistics taken over all ranks: (sum dy', sum dy' xhat) per channel as an fp64 record summed over the ranks by `sync`, divided by the
+    global row count on the device.  dgamma / dbeta accumulate this rank's sums (the gradient all-reduce adds the ranks, as for every other parameter)."""
+    M, C_ = x2.shape
+    dx = torch.empty_like(x2)
+    dres = torch.empty_like(x2) if want_dres else None
+    rec = torch.empty(2 * C_, dtype=torch.float64, device=x2.device)
+    partials = batchnorm_scratch(M, C_, x2.device)
+    check(L.lib().maed_batchnorm_bwd_reduce_local(_p(x2), _p(dy2), _p(mask), _p(mean), _p(mean_lo), _p(rstd), _p(gamma), _p(beta), _p(partials), _p(rec),
+                                                  _p(dgamma), _p(dbeta), M, C_, int(relu), dt_code(x2.dtype), _stream()), "batchnorm_bwd_reduce_local")
+    sync.all_reduce(rec)
+    check(L.lib().maed_batchnorm_bwd_apply_dev(_p(x2), _p(dy2), _p(mask), _p(mean), _p(mean_lo), _p(rstd), _p(gamma), _p(beta), _p(rec), _p(count), _p(dx), _p(dres), M, C_,
+                                               int(relu), dt_code(x2.dtype), _stream()), "batchnorm_bwd_apply_dev")
+    return dx, dres
+
+
+class SyncBatchNormTorchFn(torch.autograd.Function):
+    """The framework composition of batchnorm_stats_sync / batchnorm_bwd_sync for tensors the library does not take (host tensors without the simulator, channel
+    counts that are no multiple of 8): y = gamma (x - mean) rstd + beta with the statistics of all ranks, the same records and formulas in fp64 torch operations.
+    The residual add and the ReLU stay with autograd (resnet.BatchNorm2d.forward)."""
+
+    @staticmethod
+    def forward(ctx, x, gamma, beta, running_mean, running_var, momentum, eps, sync):
+        C_ = x.shape[1]
+        x64 = x.detach().double().transpose(0, 1).reshape(C_, -1)
+        rec = torch.cat([torch.stack([x64.sum(1), (x64 * x64).sum(1)], 1).reshape(-1), x64.new_full((1,), x64.shape[1])])
+        sync.all_reduce(rec)
+        count = rec[2 * C_]
+        s = rec[:2 * C_].view(C_, 2)
+        mean = s[:, 0] / count
+        var = (s[:, 1] / count - mean * mean).clamp_min(0.0)
+        rstd = torch.rsqrt(var + eps)
+        with torch.no_grad():
+            if running_mean is not None:
+                running_mean.copy_((1.0 - momentum) * running_mean.double() + momentum * mean)
+            if running_var is not None:
+                running_var.copy_((1.0 - momentum) * running_var.double() + momentum * torch.where(count > 1.0, var * (count / (count - 1.0)), var))
+        shape = (1, C_) + (1,) * (x.dim() - 2)
+        xhat = (x.detach().double() - mean.view(shape)) * rstd.view(shape)
+        ctx.save_for_backward(xhat, rstd, gamma, count)
+        ctx.sync, ctx.shape, ctx.dtype = sync, shape, x.dtype
+        return (xhat * gamma.double().view(shape) + beta.double().view(shape)).to(x.dtype)
+
+    @staticmethod
+    def backward(ctx, dy):
+        xhat, rstd, gamma, count = ctx.saved_tensors
+        C_ = xhat.shape[1]
+        dy64 = dy.double()
+        dims = [d for d in range(dy.dim()) if d != 1]
+        s0, s1 = dy64.sum(dims), (dy64 * xhat).sum(dims)
+        rec = torch.stack([s0, s1], 1).reshape(-1)
+        ctx.sync.all_reduce(rec)
+        r = rec.view(C_, 2) / count
+        dx = (gamma.double() * rstd).view(ctx.shape) * (dy64 - r[:, 0].view(ctx.shape) - xhat * r[:, 1].view(ctx.shape))
+        return dx.to(ctx.dtype), s1.to(gamma.dtype), s0.to(gamma.dtype), None, None, None, None, None
+
+
 def _rows(t):
     """(N, C, H, W) channels_last -> its (N*H*W, C) row matrix (a view)"""
     N, C_, H, W = t.shape
@@ -1885,16 +1981,23 @@ def _rows(t):
 class BatchNormFn(torch.autograd.Function):
     """y = act(BatchNorm2d(x) [+ residual]) on channels_last tensors (maed_batchnorm_*).  training: batch statistics, `buffers` = (running_mean, running_var) or None
     are updated in place; otherwise the statistics are the running buffers (frozen in the backward).  Saved for the backward: x, mean / rstd (C floats each) and --
-    only when a residual was added before the ReLU -- one bit per element; without a residual the ReLU decision is recomputed from x."""
+    only when a residual was added before the ReLU -- one bit per element; without a residual the ReLU decision is recomputed from x.
+    sync (a StatSync with .active, training only): the batch statistics and the backward's two sums are taken over the rows of all ranks -- one all-reduce of an
+    fp64 record per direction (batchnorm_stats_sync / batchnorm_bwd_sync); otherwise exactly the one-rank calls."""
 
     @staticmethod
-    def forward(ctx, x, residual, gamma, beta, buffers, training, momentum, eps, relu):
+    def forward(ctx, x, residual, gamma, beta, buffers, training, momentum, eps, relu, sync=None):
         N, C_, H, W = x.shape
         x = x.contiguous(memory_format=torch.channels_last)
         if residual is not None:
             residual = residual.contiguous(memory_format=torch.channels_last).to(x.dtype)
         x2 = _rows(x)
-        if training:
+        sync = sync if (training and sync is not None and sync.active) else None
+        count = None
+        if sync is not None:
+            rm, rv = buffers if buffers is not None else (None, None)
+            mean, rstd, mean_lo, count = batchnorm_stats_sync(x2, eps, sync, rm, rv, momentum)
+        elif training:
             rm, rv = buffers if buffers is not None else (None, None)
             mean, rstd, mean_lo = batchnorm_stats(x2, eps, rm, rv, momentum)
         else:
@@ -1902,22 +2005,25 @@ class BatchNormFn(torch.autograd.Function):
             mean, rstd, mean_lo = rm.float().clone(), torch.rsqrt(rv.float() + eps), None
         need_mask = relu and residual is not None and any(ctx.needs_input_grad[:4])
         y2, mask = batchnorm_apply(x2, mean, rstd, gamma, beta, None if residual is None else _rows(residual), relu, want_mask=need_mask)
-        ctx.save_for_backward(x, mask, mean, rstd, gamma, beta, mean_lo)
-        ctx.relu, ctx.has_res, ctx.frozen = relu, residual is not None, not training
+        ctx.save_for_backward(x, mask, mean, rstd, gamma, beta, mean_lo, count)
+        ctx.relu, ctx.has_res, ctx.frozen, ctx.sync = relu, residual is not None, not training, sync
         return y2.view(N, H, W, C_).permute(0, 3, 1, 2)
 
     @staticmethod
     def backward(ctx, dy):
-        x, mask, mean, rstd, gamma, beta, mean_lo = ctx.saved_tensors
+        x, mask, mean, rstd, gamma, beta, mean_lo, count = ctx.saved_tensors
         N, C_, H, W = x.shape
         dy = dy.contiguous(memory_format=torch.channels_last).to(x.dtype)
         want_affine = ctx.needs_input_grad[2] or ctx.needs_input_grad[3]
         dgamma = torch.zeros(C_, dtype=torch.float32, device=x.device) if want_affine else None
         dbeta = torch.zeros(C_, dtype=torch.float32, device=x.device) if want_affine else None
-        dx2, dres2 = batchnorm_bwd(_rows(x), _rows(dy), mean, rstd, gamma, beta, mask, ctx.relu, ctx.frozen, dgamma, dbeta, want_dres=ctx.has_res, mean_lo=mean_lo)
+        if ctx.sync is not None:
+            dx2, dres2 = batchnorm_bwd_sync(_rows(x), _rows(dy), mean, rstd, gamma, beta, count, ctx.sync, mask, ctx.relu, dgamma, dbeta, want_dres=ctx.has_res, mean_lo=mean_lo)
+        else:
+            dx2, dres2 = batchnorm_bwd(_rows(x), _rows(dy), mean, rstd, gamma, beta, mask, ctx.relu, ctx.frozen, dgamma, dbeta, want_dres=ctx.has_res, mean_lo=mean_lo)
         dx = dx2.view(N, H, W, C_).permute(0, 3, 1, 2)
         dres = dres2.view(N, H, W, C_).permute(0, 3, 1, 2) if dres2 is not None else None
-        return dx, dres, dgamma, dbeta, None, None, None, None, None
+        return dx, dres, dgamma, dbeta, None, None, None, None, None, None
 
 
 class MaxPool3s2P1Fn(torch.autograd.Function):

@@ -8,7 +8,8 @@ the convolutions are the library's GEMM / implicit-GEMM / stem kernels the Group
 weight images (ops.WeightImageFn); a shape outside a kernel's precondition takes the framework's convolution.
 
 The norm layer is NOT a torch.nn.modules.batchnorm._BatchNorm: torch.nn.SyncBatchNorm.convert_sync_batchnorm (reference train.py:95) leaves it in place.
-Under more than one rank every rank normalises with its own batch (no cross-rank statistics; docs/design/12_cnn_encoder.md).
+Statistics over the batch of all ranks are opt-in: convert_sync_batchnorm below (docs/design/16_sync_batchnorm.md); without it every rank normalises with its
+own batch.
 """
 import os
 from collections import OrderedDict
@@ -83,24 +84,44 @@ class BatchNorm2d(nn.Module):
         self.register_buffer("running_mean", torch.zeros(num_features))
         self.register_buffer("running_var", torch.ones(num_features))
         self.register_buffer("num_batches_tracked", torch.tensor(0, dtype=torch.long))
+        self.sync = None        # ops.StatSync (convert_sync_batchnorm): training statistics over the batch of all ranks
 
     def extra_repr(self):
         return f"{self.num_features}, eps={self.eps}, momentum={self.momentum}"
 
     def forward(self, x, residual=None, relu=False):
         rows = x.numel() // x.shape[1]
-        if self.training and rows <= 1:
+        sync = self.sync if (self.training and self.sync is not None and self.sync.active) else None
+        if self.training and rows <= 1 and (sync is None or sync.world == 1):
             raise ValueError(f"Expected more than 1 value per channel when training, got input size {tuple(x.shape)}")
+        if sync is not None and rows < 1:
+            raise ValueError(f"statistics over all ranks need at least one row on every rank, got input size {tuple(x.shape)}")
         if _LIB_BN and ops.on_library_device(x) and bn_qualifies(x.shape[1], rows, x.dtype):
             if self.training:
                 self.num_batches_tracked.add_(1)
-            return ops.BatchNormFn.apply(x, residual, self.weight, self.bias, (self.running_mean, self.running_var), self.training, self.momentum, self.eps, relu)
+            return ops.BatchNormFn.apply(x, residual, self.weight, self.bias, (self.running_mean, self.running_var), self.training, self.momentum, self.eps, relu, sync)
         if self.training:
             self.num_batches_tracked.add_(1)
-        y = F.batch_norm(x, self.running_mean, self.running_var, self.weight, self.bias, self.training, self.momentum, self.eps)
+        if sync is not None:
+            y = ops.SyncBatchNormTorchFn.apply(x, self.weight, self.bias, self.running_mean, self.running_var, self.momentum, self.eps, sync)
+        else:
+            y = F.batch_norm(x, self.running_mean, self.running_var, self.weight, self.bias, self.training, self.momentum, self.eps)
         if residual is not None:
             y = y + residual
         return F.relu(y) if relu else y
+
+
+def convert_sync_batchnorm(module, process_group=None, comm=None, force_collectives=False):
+    """torch.nn.SyncBatchNorm.convert_sync_batchnorm (reference train.py:95) for this module's norm layers: every BatchNorm2d under `module` takes its training
+    statistics over the batch of all ranks of `process_group` (torch.distributed; None = the default group) or of `comm` (a ddp.RcclComm).  The modules stay in
+    place (state-dict keys do not change); one reducer is shared by all of them.  No collective is issued in eval mode or in a world of one, unless
+    force_collectives asks for them there.  The stat collectives and the gradient buckets share a communicator: every rank must issue both kinds from one host
+    thread, in program order (docs/design/16_sync_batchnorm.md).  Returns `module`."""
+    sync = ops.StatSync(process_group, comm, force_collectives)
+    for m in module.modules():
+        if isinstance(m, BatchNorm2d):
+            m.sync = sync
+    return module
 
 
 class MaxPool3s2P1(nn.Module):
