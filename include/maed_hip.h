@@ -794,6 +794,31 @@ int maed_render_mesh(const float* verts, const int32_t* faces, const int32_t* fa
                      const float* rot, const uint8_t* frames_in, uint8_t* out, int32_t* face_id, float* depth, int B, int V, int n_faces, int H, int W,
                      const float* base_host, float wire_px, int flags, void* workspace, size_t workspace_bytes, void* stream);
 
+/* Many meshes per frame in one pass: M meshes that share one face list are drawn into B frames, mesh m into frame mesh_frame_host[m], with ONE visibility buffer
+ * and ONE resolve pass.  The LAYER of a mesh is its position among the meshes of its frame, in array order.
+ *   verts (M, V, 3), cam (M, 4), rot (M, 3, 3) or NULL, faces / faces_host / vf_off / vf_idx: as in maed_render_mesh, per mesh instead of per frame
+ *   colour           DEVICE fp32 (M, 3): base colour per mesh (needed when out != NULL)
+ *   zoff             DEVICE fp32 (M) or NULL: per-mesh depth offset, MAED_RENDER_SHARED_DEPTH only (MAED_ERR_ARG otherwise)
+ *   mesh_frame_host  HOST int32 (M): non-decreasing, every value in [0, B); anything else is MAED_ERR_ARG before any launch.  The call builds the frame -> first
+ *                    mesh table from it and hands it to the device in kernel arguments: the array may be freed on return, the call does not wait for the stream
+ *   frames_in, out   uint8 (B, H, W, 3) as in maed_render_mesh; a frame without a mesh leaves the call as frames_in (black if NULL).  M = 0 is legal
+ *   mesh_id          int32 (B, H, W) or NULL: index 0 .. M-1 of the visible mesh, -1 where nothing covers;  face_id, depth: its visible face and depth
+ *   flags            default = PAINTER: key = ((255 - layer) << 56) | (ord32(z) << 24) | face.  The 64-bit minimum is the highest layer that covers the pixel, then
+ *                    the nearest fragment, then the lowest face: bit for bit what M calls of maed_render_mesh in array order, each over the previous result, give.
+ *                    depth = the winner's ndc_z.
+ *                    MAED_RENDER_SHARED_DEPTH: z' = z + zoff[m] (one fp32 add, after the |z| <= 1 clip test on z), key = (ord32(z') << 32) | (layer << 24) | face.
+ *                    The nearest fragment of all meshes wins, an exact tie goes to the lower layer, then the lower face.  depth = z'.
+ *                    form << MAED_RENDER_FORM_SHIFT as in maed_render_mesh (same bits in every form).  MAED_RENDER_WIREFRAME: MAED_ERR_UNSUPPORTED (a pixel that
+ *                    fails the edge test would have to show the layer below, which one winner per pixel cannot express)
+ *   workspace        maed_render_people_workspace(M, B, V, n_faces, H, W, flags) bytes, 16-byte aligned
+ * Limits (MAED_ERR_ARG, the message names the limit): at most 255 meshes per frame; n_faces < 2^24; M V, M n_faces, B H W < 2^31; H, W <= 16384. */
+#define MAED_RENDER_SHARED_DEPTH 4
+size_t maed_render_people_workspace(int M, int B, int V, int n_faces, int H, int W, int flags);
+int maed_render_people(const float* verts, const int32_t* faces, const int32_t* faces_host, const int32_t* vf_off, const int32_t* vf_idx, const float* cam,
+                       const float* rot, const float* colour, const float* zoff, const int32_t* mesh_frame_host, const uint8_t* frames_in, uint8_t* out,
+                       int32_t* mesh_id, int32_t* face_id, float* depth, int M, int B, int V, int n_faces, int H, int W, int flags, void* workspace,
+                       size_t workspace_bytes, void* stream);
+
 /* ---- stage-1 encoder (MAED(encoder='cnn'), lib/models/maed.py:35-37: torchvision-layout ResNet-50): BatchNorm2d, MaxPool2d(3, 2, 1), global average pool ----
  * Activations are channels_last: row-major (M = N*H*W rows, C) in `dtype` (MAED_F32 / MAED_BF16), C % 8 == 0, M < 2^31, 16-byte aligned; mean / rstd / gamma /
  * beta / running buffers / sums are fp32 (C), 16-byte aligned.  No atomics: every result is bit-identical from run to run.

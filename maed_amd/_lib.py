@@ -203,6 +203,8 @@ SIGNATURES = {
     "maed_clip_preprocess": (i32, [vp, i64, vp, vp, vp, vp, i32, i32, i32, i32, C.POINTER(f32), i32, i32, vp, vp, C.c_size_t, vp]),
     "maed_render_mesh_workspace": (C.c_size_t, [i32, i32, i32, i32, i32, i32]),
     "maed_render_mesh": (i32, [vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, i32, i32, i32, i32, i32, C.POINTER(f32), f32, i32, vp, C.c_size_t, vp]),
+    "maed_render_people_workspace": (C.c_size_t, [i32, i32, i32, i32, i32, i32, i32]),
+    "maed_render_people": (i32, [vp] * 15 + [i32] * 7 + [vp, C.c_size_t, vp]),
     "maed_batchnorm_chunks": (i32, [i64]),
     "maed_batchnorm_stats": (i32, [vp, i64, i32, i32, vp, f32, vp, vp, vp, vp, vp, f32, vp]),
     "maed_batchnorm_finalize": (i32, [vp, i32, i32, C.c_double, f32, vp, vp, vp, vp, vp, f32, vp]),

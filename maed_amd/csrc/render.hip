@@ -15,6 +15,9 @@
 //   SPLIT  triangles whose clamped bounding box has at most RENDER_SMALL_BOX pixel centres on one lane; the others are appended to a queue (one vector atomic add
 //          each) and a second launch gives each of them a workgroup.  The automatic choice.
 // Only vector atomics (global_atomic_umin_x2, global_atomic_add) and plain stores are used.
+//
+// Many meshes per frame (maed_render_people): the same passes over M meshes and ONE visibility buffer of B frames; every kernel below is a template over how a mesh
+// finds its frame and how a fragment becomes a 64-bit key (OneMesh: the layout above; Layered: the painter and the shared-depth layouts, see the struct).
 #include "common.cuh"
 #ifdef MAED_HOSTSIM
 #include "render_support.h"
@@ -30,6 +33,8 @@ constexpr int RENDER_MAX_DIM = 16384;                 // viewport limit: pixel c
 constexpr float RENDER_COORD_CLAMP = 1073741824.0f;   // 2^30 sub-pixel units: snapped vertex coordinates are clamped here (4 194 304 px from the origin)
 constexpr int RENDER_SMALL_BOX = 256;                 // SPLIT form: bounding boxes up to this many pixel centres stay on a lane
 constexpr unsigned long long RENDER_EMPTY = ~0ull;
+constexpr int RENDER_MAX_FACES = 1 << 24;             // many meshes per frame: the key holds 24 bits of face index and 8 bits of layer
+constexpr int RENDER_MAX_LAYERS = 255;
 #ifdef MAED_HOSTSIM
 constexpr int RENDER_THREADS = 64;                    // one host thread per lane: small workgroups, few of them, grid-stride loops do the rest
 constexpr int RENDER_MAX_GRID = 4;
@@ -154,22 +159,78 @@ __device__ __forceinline__ float depth_at(const Tri& t, int64_t w0, int64_t w1, 
     return ((l0 * t.z[0] + l1 * t.z[1]) + l2 * t.z[2]) + 0.0f;
 }
 
-__device__ __forceinline__ unsigned long long depth_key(float z, int face) {
+// order-preserving bits of a float: unsigned comparison of ord32(a), ord32(b) is the comparison of a, b
+__device__ __forceinline__ uint32_t ord32(float z) {
     const uint32_t u = __float_as_uint(z);
-    const uint32_t ord = (u & 0x80000000u) ? ~u : (u | 0x80000000u);
-    return ((unsigned long long)ord << 32) | (unsigned long long)(uint32_t)face;
+    return (u & 0x80000000u) ? ~u : (u | 0x80000000u);
 }
-__device__ __forceinline__ float key_depth(unsigned long long key) {
-    const uint32_t ord = (uint32_t)(key >> 32);
-    return __uint_as_float((ord & 0x80000000u) ? (ord & 0x7fffffffu) : ~ord);
-}
+__device__ __forceinline__ float ord32_depth(uint32_t ord) { return __uint_as_float((ord & 0x80000000u) ? (ord & 0x7fffffffu) : ~ord); }
 
-__device__ __forceinline__ void fragment(const Tri& t, int64_t w0, int64_t w1, int64_t w2, int face, unsigned long long* __restrict__ cell) {
+// ---- how a mesh finds its frame and a fragment its key ------------------------------------------------------------------------------------
+// A mode gives, per mesh, a Ctx {frame, key(z, face)} for the raster pass and, per pixel, decode(key, frame) -> mesh, face, depth for the resolve pass.
+struct Winner { int mesh, face; float depth; };
+
+// one mesh per frame: mesh b draws into frame b;  key = (ord32(z) << 32) | face
+struct OneMesh {
+    int unused;
+    struct Ctx {
+        int frame;
+        __device__ __forceinline__ unsigned long long key(float z, int face) const { return ((unsigned long long)ord32(z) << 32) | (unsigned long long)(uint32_t)face; }
+    };
+    __device__ __forceinline__ Ctx ctx(int m) const { return Ctx{m}; }
+    __device__ __forceinline__ bool decode(unsigned long long key, int b, Winner& w) const {
+        w.mesh = b; w.face = (int)(uint32_t)key; w.depth = ord32_depth((uint32_t)(key >> 32));
+        return true;
+    }
+    __device__ __forceinline__ const float* base(int, const float* shade_base) const { return shade_base; }
+    __device__ __forceinline__ void put_mesh(int64_t, int) const {}
+};
+
+// many meshes per frame: first (B + 1) is the frame -> first mesh table, mesh_frame (M) its inverse; the layer of mesh m is m - first[mesh_frame[m]] (< 255).
+//   painter       key = ((255 - layer) << 56) | (ord32(z) << 24) | face        the highest layer that covers the pixel, then the nearest fragment, then the lowest face
+//   shared depth  key = (ord32(z + zoff[m]) << 32) | (layer << 24) | face      the nearest fragment of all meshes, then the lowest layer, then the lowest face
+// No key equals RENDER_EMPTY: faces are below 2^24 - 1 and layers below 255.
+struct Layered {
+    const int* first;
+    const int* mesh_frame;
+    const float* zoff;                                 // (M) or null; shared depth only
+    const float* colour;                               // (M, 3)
+    int* mesh_id;                                      // (B, H, W) or null
+    int shared;
+    struct Ctx {
+        int frame;
+        uint32_t layer;
+        float zoff;
+        int shared;
+        __device__ __forceinline__ unsigned long long key(float z, int face) const {
+            if (shared) return ((unsigned long long)ord32(z + zoff) << 32) | (unsigned long long)((layer << 24) | (uint32_t)face);
+            return ((unsigned long long)(255u - layer) << 56) | ((unsigned long long)ord32(z) << 24) | (unsigned long long)(uint32_t)face;
+        }
+    };
+    __device__ __forceinline__ Ctx ctx(int m) const {
+        const int b = mesh_frame[m];
+        return Ctx{b, (uint32_t)(m - first[b]) & 0xffu, (shared && zoff) ? zoff[m] : 0.0f, shared};
+    }
+    __device__ __forceinline__ bool decode(unsigned long long key, int b, Winner& w) const {
+        uint32_t layer, ord;
+        if (shared) { ord = (uint32_t)(key >> 32); layer = (uint32_t)(key >> 24) & 0xffu; }
+        else { ord = (uint32_t)(key >> 24); layer = 255u - (uint32_t)(key >> 56); }
+        const int m0 = first[b];
+        if ((int)layer >= first[b + 1] - m0) return false;         // (never a gather through a layer the frame does not have)
+        w.mesh = m0 + (int)layer; w.face = (int)((uint32_t)key & 0xffffffu); w.depth = ord32_depth(ord);
+        return true;
+    }
+    __device__ __forceinline__ const float* base(int m, const float*) const { return colour + (size_t)m * 3; }
+    __device__ __forceinline__ void put_mesh(int64_t i, int m) const { if (mesh_id) mesh_id[i] = m; }
+};
+
+template <class Ctx>
+__device__ __forceinline__ void fragment(const Tri& t, int64_t w0, int64_t w1, int64_t w2, int face, unsigned long long* __restrict__ cell, const Ctx& c) {
     if ((w0 + t.bias[0]) < 0 || (w1 + t.bias[1]) < 0 || (w2 + t.bias[2]) < 0) return;
     float l0, l1, l2;
     const float z = depth_at(t, w0, w1, w2, l0, l1, l2);
-    if (!(fabsf(z) <= 1.0f)) return;                   // GL clip volume (also drops NaN)
-    atomicMin(cell, depth_key(z, face));
+    if (!(fabsf(z) <= 1.0f)) return;                   // GL clip volume (also drops NaN); a mesh's depth offset is added after it
+    atomicMin(cell, c.key(z, face));
 }
 
 __device__ __forceinline__ bool load_tri(const int* __restrict__ faces, const ProjV* __restrict__ pv, int f, int V, int H, int W, Tri& t, bool& bad) {
@@ -180,9 +241,10 @@ __device__ __forceinline__ bool load_tri(const int* __restrict__ faces, const Pr
 }
 
 // ---- raster, one triangle per lane; split != 0: boxes above RENDER_SMALL_BOX go to the queue instead ------------------------------------
+template <class Mode>
 __global__ __launch_bounds__(RENDER_THREADS) void render_raster_lane_kernel(const int* __restrict__ faces, const ProjV* __restrict__ pv, int B, int V, int n_faces, int H,
                                                                             int W, int split, unsigned long long* __restrict__ vis, unsigned* __restrict__ counters,
-                                                                            int* __restrict__ queue) {
+                                                                            int* __restrict__ queue, Mode mode) {
     const int64_t n = (int64_t)B * n_faces;
     for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (int64_t)gridDim.x * blockDim.x) {
         const int b = (int)(i / n_faces), f = (int)(i - (int64_t)b * n_faces);
@@ -193,17 +255,18 @@ __global__ __launch_bounds__(RENDER_THREADS) void render_raster_lane_kernel(cons
             continue;
         }
         if (split && (int64_t)(t.x1 - t.x0 + 1) * (t.y1 - t.y0 + 1) > RENDER_SMALL_BOX) {
-            queue[atomicAdd(counters, 1u)] = (int)i;   // (at most B * n_faces entries: the queue's size)
+            queue[atomicAdd(counters, 1u)] = (int)i;   // (at most B * n_faces entries: the queue's size; the entry names the mesh as well as the face)
             continue;
         }
-        unsigned long long* frame = vis + (size_t)b * H * W;
+        const typename Mode::Ctx c = mode.ctx(b);
+        unsigned long long* frame = vis + (size_t)c.frame * H * W;
         const int Px0 = t.x0 * 256 + 128;
         const int64_t s0 = (int64_t)t.dy[0] * 256, s1 = (int64_t)t.dy[1] * 256, s2 = (int64_t)t.dy[2] * 256;
         for (int y = t.y0; y <= t.y1; ++y) {
             const int Py = y * 256 + 128;
             int64_t w0 = edge_at(t, 0, Px0, Py), w1 = edge_at(t, 1, Px0, Py), w2 = edge_at(t, 2, Px0, Py);
             for (int x = t.x0; x <= t.x1; ++x) {
-                fragment(t, w0, w1, w2, f, frame + (size_t)y * W + x);
+                fragment(t, w0, w1, w2, f, frame + (size_t)y * W + x, c);
                 w0 += s0; w1 += s1; w2 += s2;          // (exact: integers)
             }
         }
@@ -211,9 +274,10 @@ __global__ __launch_bounds__(RENDER_THREADS) void render_raster_lane_kernel(cons
 }
 
 // ---- raster, one queued triangle per workgroup -----------------------------------------------------------------------------------------
+template <class Mode>
 __global__ __launch_bounds__(RENDER_THREADS) void render_raster_large_kernel(const int* __restrict__ faces, const ProjV* __restrict__ pv, int B, int V, int n_faces, int H,
                                                                              int W, unsigned long long* __restrict__ vis, const unsigned* __restrict__ counters,
-                                                                             const int* __restrict__ queue) {
+                                                                             const int* __restrict__ queue, Mode mode) {
     const unsigned count = min((int64_t)counters[0], (int64_t)B * n_faces);
     for (unsigned q = blockIdx.x; q < count; q += gridDim.x) {
         const int i = queue[q];
@@ -222,13 +286,14 @@ __global__ __launch_bounds__(RENDER_THREADS) void render_raster_large_kernel(con
         Tri t;
         bool bad;
         if (!load_tri(faces, pv + (size_t)b * V, f, V, H, W, t, bad)) continue;
-        unsigned long long* frame = vis + (size_t)b * H * W;
+        const typename Mode::Ctx c = mode.ctx(b);
+        unsigned long long* frame = vis + (size_t)c.frame * H * W;
         const int bw = t.x1 - t.x0 + 1;
         const int64_t np = (int64_t)bw * (t.y1 - t.y0 + 1);
         for (int64_t p = threadIdx.x; p < np; p += blockDim.x) {
             const int yy = (int)(p / bw), x = t.x0 + (int)(p - (int64_t)yy * bw), y = t.y0 + yy;
             const int Px = x * 256 + 128, Py = y * 256 + 128;
-            fragment(t, edge_at(t, 0, Px, Py), edge_at(t, 1, Px, Py), edge_at(t, 2, Px, Py), f, frame + (size_t)y * W + x);
+            fragment(t, edge_at(t, 0, Px, Py), edge_at(t, 1, Px, Py), edge_at(t, 2, Px, Py), f, frame + (size_t)y * W + x, c);
         }
     }
 }
@@ -237,21 +302,25 @@ __global__ __launch_bounds__(RENDER_THREADS) void render_raster_large_kernel(con
 // colour = base * (0.3 + g * sum_i max(0, n . l_i)), lights at (0,-1,1), (0,1,1), (1,1,2) in the camera frame (renderer.py:55-67), g = RENDER_LIGHT_GAIN
 constexpr float RENDER_AMBIENT = 0.3f, RENDER_LIGHT_GAIN = 0.3f;
 
-struct Px { int covered; int face; float depth; uint8_t rgb[3]; int draw; };
+struct Px { int covered; int mesh; int face; float depth; uint8_t rgb[3]; int draw; };
 
+// b: the pixel's frame.  The winner's mesh (b itself with one mesh per frame) names the block of pv / pos / nrm that is gathered and the base colour.
+template <class Mode>
 __device__ inline Px resolve_pixel(unsigned long long key, int b, int x, int y, const int* __restrict__ faces, const ProjV* __restrict__ pv, const Vec4* __restrict__ pos,
-                                   const Vec4* __restrict__ nrm, int V, int n_faces, int H, int W, const Shade& sh, bool want_colour) {
+                                   const Vec4* __restrict__ nrm, int V, int n_faces, int H, int W, const Shade& sh, bool want_colour, const Mode& mode) {
     Px o;
-    o.covered = 0; o.face = -1; o.depth = __uint_as_float(0x7f800000u); o.draw = 0; o.rgb[0] = o.rgb[1] = o.rgb[2] = 0;
+    o.covered = 0; o.mesh = -1; o.face = -1; o.depth = __uint_as_float(0x7f800000u); o.draw = 0; o.rgb[0] = o.rgb[1] = o.rgb[2] = 0;
     if (key == RENDER_EMPTY) return o;
-    const int f = (int)(uint32_t)key;
+    Winner win;
+    if (!mode.decode(key, b, win)) return o;
+    const int f = win.face;
     if ((unsigned)f >= (unsigned)n_faces) return o;
     const int i0 = faces[f * 3], i1 = faces[f * 3 + 1], i2 = faces[f * 3 + 2];
     if ((unsigned)i0 >= (unsigned)V || (unsigned)i1 >= (unsigned)V || (unsigned)i2 >= (unsigned)V) return o;
-    const size_t vb = (size_t)b * V;
+    const size_t vb = (size_t)win.mesh * V;
     Tri t;
     if (!tri_setup(pv[vb + i0], pv[vb + i1], pv[vb + i2], H, W, t)) return o;
-    o.covered = 1; o.face = f; o.depth = key_depth(key); o.draw = 1;
+    o.covered = 1; o.mesh = win.mesh; o.face = f; o.depth = win.depth; o.draw = 1;
     if (!want_colour) return o;
     const int Px_ = x * 256 + 128, Py_ = y * 256 + 128;
     const int64_t w0 = edge_at(t, 0, Px_, Py_), w1 = edge_at(t, 1, Px_, Py_), w2 = edge_at(t, 2, Px_, Py_);
@@ -284,19 +353,21 @@ __device__ inline Px resolve_pixel(unsigned long long key, int b, int x, int y, 
         sum += fmaxf(d, 0.f);
     }
     const float lum = RENDER_AMBIENT + RENDER_LIGHT_GAIN * sum;
+    const float* base = mode.base(win.mesh, sh.base);
 #pragma unroll
     for (int c = 0; c < 3; ++c) {
-        const float v = fminf(fmaxf(sh.base[c] * lum, 0.f), 1.f);
+        const float v = fminf(fmaxf(base[c] * lum, 0.f), 1.f);
         o.rgb[c] = (uint8_t)(int)(v * 255.0f);
     }
     return o;
 }
 
 // A thread owns four consecutive pixels of the flattened (B * H * W) batch = 12 bytes of frame = three aligned dwords; the last n % 4 pixels go bytewise.
+template <class Mode>
 __global__ __launch_bounds__(RENDER_THREADS) void render_resolve_kernel(const unsigned long long* __restrict__ vis, const int* __restrict__ faces, const ProjV* __restrict__ pv,
                                                                         const Vec4* __restrict__ pos, const Vec4* __restrict__ nrm, const uint8_t* frames_in,
                                                                         uint8_t* out, int* __restrict__ face_id, float* __restrict__ depth, int B, int V, int n_faces,
-                                                                        int H, int W, Shade sh) {
+                                                                        int H, int W, Shade sh, Mode mode) {
     const int64_t n = (int64_t)B * H * W, nq = (n + 3) / 4, hw = (int64_t)H * W;
     for (int64_t q = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; q < nq; q += (int64_t)gridDim.x * blockDim.x) {
         const int64_t first = q * 4;
@@ -320,7 +391,8 @@ __global__ __launch_bounds__(RENDER_THREADS) void render_resolve_kernel(const un
             const int b = (int)(i / hw);
             const int64_t r = i - (int64_t)b * hw;
             const int y = (int)(r / W), x = (int)(r - (int64_t)y * W);
-            const Px o = resolve_pixel(vis[i], b, x, y, faces, pv, pos, nrm, V, n_faces, H, W, sh, out != nullptr);
+            const Px o = resolve_pixel(vis[i], b, x, y, faces, pv, pos, nrm, V, n_faces, H, W, sh, out != nullptr, mode);
+            mode.put_mesh(i, o.mesh);
             if (face_id) face_id[i] = o.face;
             if (depth) depth[i] = o.depth;
             if (o.draw) { bytes[3 * k] = o.rgb[0]; bytes[3 * k + 1] = o.rgb[1]; bytes[3 * k + 2] = o.rgb[2]; }
@@ -340,28 +412,71 @@ __global__ __launch_bounds__(RENDER_THREADS) void render_resolve_kernel(const un
     }
 }
 
+// ---- host tables -> device, as kernel arguments -------------------------------------------------------------------------------------------
+// The frame -> first mesh table and its inverse are built on the host per call.  They travel in the kernel-argument block of a one-workgroup launch (a copy the
+// runtime takes at launch time): no staging copy from pageable memory, so the call neither waits for the stream nor keeps a host buffer alive.
+constexpr int RENDER_TABLE_CHUNK = 512;
+struct TableChunk { int v[RENDER_TABLE_CHUNK]; };
+__global__ __launch_bounds__(RENDER_THREADS) void render_table_kernel(TableChunk c, int n, int* __restrict__ dst) {
+    for (int i = threadIdx.x; i < n && i < RENDER_TABLE_CHUNK; i += blockDim.x) dst[i] = c.v[i];
+}
+
 inline size_t up256(size_t n) { return (n + 255) / 256 * 256; }
-struct Layout { size_t vis, pv, pos, nrm, counters, queue, total; };
-inline Layout layout(int B, int V, int n_faces, int H, int W) {
+// B frames of H x W pixels, M meshes of V vertices (M = B with one mesh per frame), table_ints of host tables
+struct Layout { size_t vis, pv, pos, nrm, counters, queue, table, total; };
+inline Layout layout(int B, int M, int V, int n_faces, int H, int W, size_t table_ints) {
     Layout l;
     size_t at = 0;
     l.vis = at; at += up256((size_t)B * H * W * 8);
-    l.pv = at; at += up256((size_t)B * V * sizeof(ProjV));
-    l.pos = at; at += up256((size_t)B * V * sizeof(Vec4));
-    l.nrm = at; at += up256((size_t)B * V * sizeof(Vec4));
+    l.pv = at; at += up256((size_t)M * V * sizeof(ProjV));
+    l.pos = at; at += up256((size_t)M * V * sizeof(Vec4));
+    l.nrm = at; at += up256((size_t)M * V * sizeof(Vec4));
     l.counters = at; at += 256;
-    l.queue = at; at += up256((size_t)B * n_faces * 4);
+    l.queue = at; at += up256((size_t)M * n_faces * 4);
+    l.table = at; at += up256(table_ints * 4);
     l.total = at;
     return l;
 }
 inline int grid_for(int64_t items) { return (int)max((int64_t)1, min((int64_t)RENDER_MAX_GRID, (items + RENDER_THREADS - 1) / RENDER_THREADS)); }
+
+struct Targets { const uint8_t* frames_in; uint8_t* out; int32_t* face_id; float* depth; };
+
+// the passes of one call: M meshes into the visibility buffer of B frames, then one resolve over the B frames
+template <class Mode>
+int run_passes(const char* who, const float* verts, const int32_t* faces, const int32_t* vf_off, const int32_t* vf_idx, const float* cam, const float* rot, const Targets& t,
+               int B, int M, int V, int n_faces, int H, int W, const Shade& sh, int flags, int form, char* ws, const Layout& l, const Mode& mode, hipStream_t st) {
+    unsigned long long* vis = (unsigned long long*)(ws + l.vis);
+    ProjV* pv = (ProjV*)(ws + l.pv);
+    Vec4* pos = (Vec4*)(ws + l.pos);
+    Vec4* nrm = (Vec4*)(ws + l.nrm);
+    unsigned* counters = (unsigned*)(ws + l.counters);
+    int* queue = (int*)(ws + l.queue);
+    const dim3 blk(RENDER_THREADS);
+    MAED_HIP(hipMemsetAsync(vis, 0xFF, (size_t)B * H * W * 8, st), who);
+    MAED_HIP(hipMemsetAsync(counters, 0, 256, st), who);
+    if (M > 0) {
+        hipLaunchKernelGGL(render_vertex_kernel, dim3(grid_for((int64_t)M * V)), blk, 0, st, verts, cam, rot, M, V, H, W, pv, pos);
+        if (t.out && !(flags & MAED_RENDER_RASTER_ONLY))
+            hipLaunchKernelGGL(render_normal_kernel, dim3(grid_for((int64_t)M * V)), blk, 0, st, (const Vec4*)pos, faces, vf_off, vf_idx, M, V, n_faces, nrm);
+        hipLaunchKernelGGL(render_raster_lane_kernel<Mode>, dim3(grid_for((int64_t)M * n_faces)), blk, 0, st, faces, (const ProjV*)pv, M, V, n_faces, H, W,
+                           (int)(form == FORM_SPLIT), vis, counters, queue, mode);
+        if (form == FORM_SPLIT)
+            hipLaunchKernelGGL(render_raster_large_kernel<Mode>, dim3(RENDER_LARGE_GRID), blk, 0, st, faces, (const ProjV*)pv, M, V, n_faces, H, W, vis,
+                               (const unsigned*)counters, (const int*)queue, mode);
+    }
+    if (!(flags & MAED_RENDER_RASTER_ONLY))
+        hipLaunchKernelGGL(render_resolve_kernel<Mode>, dim3(grid_for(((int64_t)B * H * W + 3) / 4)), blk, 0, st, (const unsigned long long*)vis, faces, (const ProjV*)pv,
+                           (const Vec4*)pos, (const Vec4*)nrm, t.frames_in, t.out, t.face_id, t.depth, B, V, n_faces, H, W, sh, mode);
+    MAED_CHECK_LAUNCH(who);
+    return MAED_OK;
+}
 
 }  // namespace
 
 extern "C" size_t maed_render_mesh_workspace(int B, int V, int n_faces, int H, int W, int flags) {
     (void)flags;
     if (B <= 0 || V <= 0 || n_faces <= 0 || H <= 0 || W <= 0) return 0;
-    return layout(B, V, n_faces, H, W).total;
+    return layout(B, B, V, n_faces, H, W, 0).total;
 }
 
 extern "C" int maed_render_mesh(const float* verts, const int32_t* faces, const int32_t* faces_host, const int32_t* vf_off, const int32_t* vf_idx, const float* cam,
@@ -386,38 +501,90 @@ extern "C" int maed_render_mesh(const float* verts, const int32_t* faces, const 
         for (int64_t i = 0; i < (int64_t)n_faces * 3; ++i)
             MAED_CHECK_ARG((uint32_t)faces_host[i] < (uint32_t)V, MAED_ERR_ARG, "render_mesh: face %lld has vertex index %d outside [0, %d)", (long long)(i / 3),
                            (int)faces_host[i], V);
-    const Layout l = layout(B, V, n_faces, H, W);
+    const Layout l = layout(B, B, V, n_faces, H, W, 0);
     MAED_CHECK_ARG(workspace && workspace_bytes >= l.total, MAED_ERR_ARG, "render_mesh: needs %zu bytes of workspace", l.total);
     MAED_CHECK_ARG(is_aligned(workspace, 16), MAED_ERR_ALIGN, "render_mesh: workspace must be 16-byte aligned");
-    char* ws = (char*)workspace;
-    unsigned long long* vis = (unsigned long long*)(ws + l.vis);
-    ProjV* pv = (ProjV*)(ws + l.pv);
-    Vec4* pos = (Vec4*)(ws + l.pos);
-    Vec4* nrm = (Vec4*)(ws + l.nrm);
-    unsigned* counters = (unsigned*)(ws + l.counters);
-    int* queue = (int*)(ws + l.queue);
-    hipStream_t st = (hipStream_t)stream;
     // measured (profiles/render_micro.txt): see docs/design/11_render.md for the choice of the automatic form
     const int form = form_in == FORM_AUTO ? FORM_SPLIT : form_in;
-    const dim3 blk(RENDER_THREADS);
-    MAED_HIP(hipMemsetAsync(vis, 0xFF, (size_t)B * H * W * 8, st), "render_mesh");
-    MAED_HIP(hipMemsetAsync(counters, 0, 256, st), "render_mesh");
-    hipLaunchKernelGGL(render_vertex_kernel, dim3(grid_for((int64_t)B * V)), blk, 0, st, verts, cam, rot, B, V, H, W, pv, pos);
-    if (out && !(flags & MAED_RENDER_RASTER_ONLY))
-        hipLaunchKernelGGL(render_normal_kernel, dim3(grid_for((int64_t)B * V)), blk, 0, st, (const Vec4*)pos, faces, vf_off, vf_idx, B, V, n_faces, nrm);
-    hipLaunchKernelGGL(render_raster_lane_kernel, dim3(grid_for((int64_t)B * n_faces)), blk, 0, st, faces, (const ProjV*)pv, B, V, n_faces, H, W, (int)(form == FORM_SPLIT), vis,
-                       counters, queue);
-    if (form == FORM_SPLIT)
-        hipLaunchKernelGGL(render_raster_large_kernel, dim3(RENDER_LARGE_GRID), blk, 0, st, faces, (const ProjV*)pv, B, V, n_faces, H, W, vis, (const unsigned*)counters,
-                           (const int*)queue);
-    if (!(flags & MAED_RENDER_RASTER_ONLY)) {
-        Shade sh;
-        for (int c = 0; c < 3; ++c) sh.base[c] = base_host ? base_host[c] : 1.0f;
-        sh.wire_px = wire_px;
-        sh.wireframe = wireframe;
-        hipLaunchKernelGGL(render_resolve_kernel, dim3(grid_for(((int64_t)B * H * W + 3) / 4)), blk, 0, st, (const unsigned long long*)vis, faces, (const ProjV*)pv,
-                           (const Vec4*)pos, (const Vec4*)nrm, frames_in, out, face_id, depth, B, V, n_faces, H, W, sh);
-    }
-    MAED_CHECK_LAUNCH("render_mesh");
-    return MAED_OK;
+    Shade sh;
+    for (int c = 0; c < 3; ++c) sh.base[c] = base_host ? base_host[c] : 1.0f;
+    sh.wire_px = wire_px;
+    sh.wireframe = wireframe;
+    return run_passes("render_mesh", verts, faces, vf_off, vf_idx, cam, rot, Targets{frames_in, out, face_id, depth}, B, B, V, n_faces, H, W, sh, flags, form, (char*)workspace,
+                      l, OneMesh{0}, (hipStream_t)stream);
 }
+
+extern "C" size_t maed_render_people_workspace(int M, int B, int V, int n_faces, int H, int W, int flags) {
+    (void)flags;
+    if (M < 0 || B <= 0 || V <= 0 || n_faces <= 0 || H <= 0 || W <= 0) return 0;
+    return layout(B, M, V, n_faces, H, W, (size_t)B + 1 + (size_t)M).total;
+}
+
+extern "C" int maed_render_people(const float* verts, const int32_t* faces, const int32_t* faces_host, const int32_t* vf_off, const int32_t* vf_idx, const float* cam,
+                                  const float* rot, const float* colour, const float* zoff, const int32_t* mesh_frame_host, const uint8_t* frames_in, uint8_t* out,
+                                  int32_t* mesh_id, int32_t* face_id, float* depth, int M, int B, int V, int n_faces, int H, int W, int flags, void* workspace,
+                                  size_t workspace_bytes, void* stream) {
+    MAED_CHECK_ARG(M >= 0 && B > 0 && V > 0 && n_faces > 0 && H > 0 && W > 0, MAED_ERR_ARG,
+                   "render_people: sizes must be positive (M %d may be 0; B %d, V %d, faces %d, viewport %d x %d)", M, B, V, n_faces, W, H);
+    MAED_CHECK_ARG(H <= RENDER_MAX_DIM && W <= RENDER_MAX_DIM, MAED_ERR_ARG,
+                   "render_people: viewport %d x %d is too large (at most %d in each direction: sub-pixel coordinates have 8 fractional bits and edge functions 64)", W, H,
+                   RENDER_MAX_DIM);
+    MAED_CHECK_ARG(n_faces < RENDER_MAX_FACES, MAED_ERR_ARG, "render_people: %d faces, the key holds a face index below 2^24 = %d", n_faces, RENDER_MAX_FACES);
+    MAED_CHECK_ARG((int64_t)B * H * W < ((int64_t)1 << 31) && (int64_t)M * n_faces < ((int64_t)1 << 31) && (int64_t)M * V < ((int64_t)1 << 31), MAED_ERR_ARG,
+                   "render_people: call too large (B H W, M n_faces and M V are each counted in 31 bits)");
+    const int shared = (flags & MAED_RENDER_SHARED_DEPTH) != 0;
+    MAED_CHECK_ARG(!(flags & MAED_RENDER_WIREFRAME), MAED_ERR_UNSUPPORTED,
+                   "render_people: no wireframe in the one-pass form (a pixel that fails the edge test shows the layer below; one winner per pixel cannot say that): "
+                   "draw the layers one after the other with maed_render_mesh");
+    const int form_in = (flags & MAED_RENDER_FORM_MASK) >> MAED_RENDER_FORM_SHIFT;
+    MAED_CHECK_ARG(form_in >= FORM_AUTO && form_in <= FORM_SPLIT, MAED_ERR_ARG, "render_people: form %d", form_in);
+    MAED_CHECK_ARG(M == 0 || (verts && faces && cam && mesh_frame_host), MAED_ERR_ARG, "render_people: null pointer");
+    MAED_CHECK_ARG(out || mesh_id || face_id || depth, MAED_ERR_ARG, "render_people: no output requested");
+    MAED_CHECK_ARG(!out || M == 0 || (vf_off && vf_idx && colour), MAED_ERR_ARG, "render_people: a colour output needs the vertex -> face CSR and the colours");
+    MAED_CHECK_ARG(!out || (is_aligned(out, 4) && (!frames_in || is_aligned(frames_in, 4))), MAED_ERR_ALIGN, "render_people: frames must be 4-byte aligned");
+    MAED_CHECK_ARG(shared || !zoff, MAED_ERR_ARG, "render_people: a depth offset needs MAED_RENDER_SHARED_DEPTH (the painter order does not compare depths between meshes)");
+    for (int m = 0, run = 0; m < M; ++m) {
+        const int b = mesh_frame_host[m];
+        MAED_CHECK_ARG(b >= 0 && b < B, MAED_ERR_ARG, "render_people: mesh %d is in frame %d, outside [0, %d)", m, b, B);
+        MAED_CHECK_ARG(m == 0 || b >= mesh_frame_host[m - 1], MAED_ERR_ARG, "render_people: mesh_frame must not decrease (mesh %d: frame %d after frame %d)", m, b,
+                       (int)mesh_frame_host[m - 1]);
+        run = (m > 0 && b == mesh_frame_host[m - 1]) ? run + 1 : 1;
+        MAED_CHECK_ARG(run <= RENDER_MAX_LAYERS, MAED_ERR_ARG, "render_people: frame %d has more than %d meshes (the key holds 8 bits of layer)", b, RENDER_MAX_LAYERS);
+    }
+    if (faces_host)
+        for (int64_t i = 0; i < (int64_t)n_faces * 3; ++i)
+            MAED_CHECK_ARG((uint32_t)faces_host[i] < (uint32_t)V, MAED_ERR_ARG, "render_people: face %lld has vertex index %d outside [0, %d)", (long long)(i / 3),
+                           (int)faces_host[i], V);
+    const size_t table_ints = (size_t)B + 1 + (size_t)M;
+    const Layout l = layout(B, M, V, n_faces, H, W, table_ints);
+    MAED_CHECK_ARG(workspace && workspace_bytes >= l.total, MAED_ERR_ARG, "render_people: needs %zu bytes of workspace", l.total);
+    MAED_CHECK_ARG(is_aligned(workspace, 16), MAED_ERR_ALIGN, "render_people: workspace must be 16-byte aligned");
+    char* ws = (char*)workspace;
+    int* table_dev = (int*)(ws + l.table);
+    hipStream_t st = (hipStream_t)stream;
+    // the table, a chunk at a time: first[j] = number of meshes in frames below j (B + 1 entries), then the frame of every mesh (M entries)
+    for (size_t at = 0, m = 0; at < table_ints; at += RENDER_TABLE_CHUNK) {
+        TableChunk c;
+        const int n = (int)std::min((size_t)RENDER_TABLE_CHUNK, table_ints - at);
+        for (int k = 0; k < RENDER_TABLE_CHUNK; ++k) {
+            const size_t j = at + k;
+            if (k >= n) { c.v[k] = 0; continue; }
+            if (j <= (size_t)B) {
+                while (m < (size_t)M && (size_t)mesh_frame_host[m] < j) ++m;
+                c.v[k] = (int)m;
+            } else {
+                c.v[k] = mesh_frame_host[j - (size_t)B - 1];
+            }
+        }
+        hipLaunchKernelGGL(render_table_kernel, dim3(1), dim3(RENDER_THREADS), 0, st, c, n, table_dev + at);
+    }
+    const int form = form_in == FORM_AUTO ? FORM_SPLIT : form_in;
+    Shade sh;
+    sh.base[0] = sh.base[1] = sh.base[2] = 1.0f;
+    sh.wire_px = 0.f;
+    sh.wireframe = 0;
+    Layered mode;
+    mode.first = table_dev; mode.mesh_frame = table_dev + B + 1; mode.zoff = zoff; mode.colour = colour; mode.mesh_id = mesh_id; mode.shared = shared;
+    return run_passes("render_people", verts, faces, vf_off, vf_idx, cam, rot, Targets{frames_in, out, face_id, depth}, B, M, V, n_faces, H, W, sh, flags, form, ws, l, mode, st);
+}
+

@@ -1829,6 +1829,60 @@ def render_mesh(verts, faces, faces_host, vf_off, vf_idx, cam, H, W, frames=None
     return out
 
 
+RENDER_SHARED_DEPTH = 4
+RENDER_MAX_LAYERS = 255
+
+
+def render_people_workspace(M, B, V, n_faces, H, W, flags=0):
+    return int(L.lib().maed_render_people_workspace(M, B, V, n_faces, H, W, flags))
+
+
+def render_people(verts, faces, faces_host, vf_off, vf_idx, cam, colour, mesh_frame, B, H, W, frames=None, rot=None, zoff=None, out=None, mesh_id=None, face_id=None,
+                  depth=None, shared_depth=False, wireframe=False, form=RENDER_FORM_AUTO):
+    """maed_render_people: M meshes into B frames in one pass.  verts fp32 (M, V, 3), cam fp32 (M, 4), rot fp32 (M, 3, 3) or None, colour fp32 (M, 3) and zoff fp32 (M)
+    or None on the device; mesh_frame a HOST numpy int32 (M), non-decreasing, values in [0, B): mesh m is drawn into frame mesh_frame[m], its layer is its position among
+    the meshes of that frame.  faces / faces_host / vf_off / vf_idx as in render_mesh.  Writes out (uint8 (B, H, W, 3), may be `frames`), mesh_id / face_id (int32
+    (B, H, W)) and depth (fp32 (B, H, W)), whichever are given.  shared_depth=False: painter order (zoff must be None); True: one depth buffer for all meshes, z + zoff.
+    wireframe=True is refused by the library (render.render_people draws it layer by layer).  No host synchronisation, current stream."""
+    M, V = int(verts.shape[0]), int(verts.shape[1])
+    n_faces = int(faces.shape[0])
+
+    def want(t, dtype, shape, name, optional=True):
+        if t is None:
+            if optional:
+                return
+            raise L.MaedHipError(f"render_people: {name} is required")
+        if t.dtype != dtype or tuple(t.shape) != tuple(shape) or not t.is_contiguous():
+            raise L.MaedHipError(f"render_people: {name} must be contiguous {dtype} of shape {tuple(shape)}, got {t.dtype} {tuple(t.shape)}")
+
+    want(verts, torch.float32, (M, V, 3), "verts", False)
+    want(faces, torch.int32, (n_faces, 3), "faces", False)
+    want(cam, torch.float32, (M, 4), "cam", False)
+    want(colour, torch.float32, (M, 3), "colour", out is None)
+    want(rot, torch.float32, (M, 3, 3), "rot")
+    want(zoff, torch.float32, (M,), "zoff")
+    want(frames, torch.uint8, (B, H, W, 3), "frames")
+    want(out, torch.uint8, (B, H, W, 3), "out")
+    want(mesh_id, torch.int32, (B, H, W), "mesh_id")
+    want(face_id, torch.int32, (B, H, W), "face_id")
+    want(depth, torch.float32, (B, H, W), "depth")
+    want(vf_off, torch.int32, (V + 1,), "vf_off")
+    want(vf_idx, torch.int32, (3 * n_faces,), "vf_idx")
+    if not isinstance(mesh_frame, _np.ndarray) or mesh_frame.dtype != _np.int32 or mesh_frame.shape != (M,) or not mesh_frame.flags.c_contiguous:
+        raise L.MaedHipError("render_people: mesh_frame must be a C-contiguous host int32 array with one entry per mesh")
+    fh = None
+    if faces_host is not None:
+        if faces_host.dtype != _np.int32 or faces_host.shape != (n_faces, 3) or not faces_host.flags.c_contiguous:
+            raise L.MaedHipError("render_people: faces_host must be a C-contiguous int32 array of the shape of faces")
+        fh = faces_host.ctypes.data
+    flags = (RENDER_WIREFRAME if wireframe else 0) | (RENDER_SHARED_DEPTH if shared_depth else 0) | (int(form) << RENDER_FORM_SHIFT)
+    need = render_people_workspace(M, B, V, n_faces, H, W, flags)
+    ws = _scratch(need, verts.device, tag="render_people") if need else None     # (need == 0: a non-positive size; the library says which)
+    check(L.lib().maed_render_people(_p(verts), _p(faces), fh, _p(vf_off), _p(vf_idx), _p(cam), _p(rot), _p(colour), _p(zoff), mesh_frame.ctypes.data if M else None,
+                                     _p(frames), _p(out), _p(mesh_id), _p(face_id), _p(depth), M, B, V, n_faces, H, W, flags, _p(ws), need, _stream()), "render_people")
+    return out
+
+
 # ----------------------------------------------------------------------------------------------
 # stage-1 encoder (maed_amd/resnet.py): BatchNorm2d, MaxPool2d(3, 2, 1), global average pool (csrc/batchnorm.hip), unstandardised weight images
 # ----------------------------------------------------------------------------------------------
