@@ -764,6 +764,41 @@ int maed_clip_preprocess(const uint8_t* src, int64_t src_bytes, const int32_t* f
                          const float* clip_f, int F, int N, int H, int W, const float* norm_host, int has_contrast, int form, float* out,
                          void* workspace, size_t workspace_bytes, void* stream);
 
+/* ---- video inference: person tracks -> smoothed crop boxes -> the tables of maed_clip_preprocess (csrc/tracks.hip; docs/design/17_video_inference.md) ------
+ * maed_track_boxes: lib/utils/smooth_bbox.py:11-123 (get_smooth_bbox_params) for K tracks at once, all series arithmetic in fp64.
+ *   kps         fp32 (K, L, J, 3) = x, y, confidence; 1 <= J <= 64
+ *   lengths     int32 (K): frames >= lengths[k] of track k are padding and are never read
+ *   vis_thresh  a keypoint is visible if confidence > vis_thresh (:51)
+ *   per frame (:38-61): invalid if no keypoint is visible or height = sqrt(dx^2 + dy^2) < 0.5 (dx, dy: extents of the visible keypoints' rectangle); otherwise
+ *               cx, cy = the rectangle's centre, scale = 150 / height
+ *   span (K, 2) int32 = first valid frame, last valid frame + 1 (:64-105); a track without a valid frame gives (-1, 0) and zero rows (the reference raises there)
+ *   invalid frames inside the span are filled linearly between the nearest valid neighbours p < i < q: x[p] + (i - p) * ((x[q] - x[p]) / (q - p))  (:94-102)
+ *   median filter of window kernel_size (odd, 1 .. 63) over the span's samples, zeros outside the series (scipy.signal.medfilt; :121-122)
+ *   Gaussian filter (:123): weights exp(-0.5 j^2 / sigma^2), j = -r .. r, r = int(4 sigma + 0.5) <= 512, divided by their sum; outside the series the index map
+ *               is scipy.ndimage's reflect (the edge sample repeated): t = (i + j) mod 2m, t >= m -> 2m - 1 - t
+ *   params      fp64 (K, L, 3) = cx, cy, scale, or NULL: the smoothed values in rows start .. end-1, zero elsewhere
+ *   boxes       fp32 (K, L, 4) = cx, cy, w, h with w = h = 150 / scale * box_scale (lib/data_utils/threedpw_utils.py:103-108), zero outside the span; a smoothed
+ *               scale of 0 (every sample of a span shorter than (kernel_size + 1) / 2) gives infinity, as the reference's division does
+ *   workspace   maed_track_boxes_workspace(K, L) bytes, 8-byte aligned: 0 up to L = 1024 (the series stay in LDS), else 48 L bytes per track.  L <= 2^24. */
+size_t maed_track_boxes_workspace(int K, int L);
+int maed_track_boxes(const float* kps, const int32_t* lengths, int K, int L, int J, double vis_thresh, int kernel_size, double sigma, double box_scale,
+                     float* boxes, double* params, int32_t* span, void* workspace, size_t workspace_bytes, void* stream);
+/* lib/utils/smooth_bbox.py:108-123 (smooth_bbox_params) alone: the median and the Gaussian filter over series fp64 (K, L, 3) that are already complete, rows
+ * 0 .. lengths[k]-1 of track k; params / boxes / workspace as above (the span of track k is (0, lengths[k])). */
+int maed_track_smooth(const double* series, const int32_t* lengths, int K, int L, int kernel_size, double sigma, double box_scale, float* boxes,
+                      double* params, void* workspace, size_t workspace_bytes, void* stream);
+/* maed_crop_tables: the four tables of maed_clip_preprocess for M crops (clips of T consecutive crops) of whole frames held in one uint8 (n_frames, img_h, img_w, 3)
+ * device buffer, which is that call's `src` (src_bytes = n_frames * img_h * img_w * 3).
+ *   boxes (n_boxes, 4) fp32 = cx, cy, w, h; box_index, frame_index int32 (M): the row of boxes / the frame of the buffer crop m uses
+ *   frame_i (M, 8)    = frame_index * img_h * img_w * 3, img_h, img_w, 3 * img_w, m / T, 0, 0, 0
+ *   frame_minv (M, 6) = [w/W 0 cx - w/2; 0 h/H cy - h/2], the patch -> frame map of lib/data_utils/transforms/crop.py:57-92 without rotation, scale jitter or
+ *                       shift, computed in fp64 from the fp32 box and rounded once
+ *   clip_i (ceil(M / T), 8), clip_f (ceil(M / T), 4) = 0 (no jitter, no flip)
+ * A box that is not finite or not positive, and an index outside its table, give the map [0 0 -2; 0 0 -2]: every tap lies outside the frame, the patch is black.
+ * Checked on the host (MAED_ERR_SHAPE; the library does not read device tables back): n_frames * img_h * img_w * 3 < 2^31, M <= 65535, W % 4 == 0. */
+int maed_crop_tables(const float* boxes, int n_boxes, const int32_t* box_index, const int32_t* frame_index, int M, int T, int n_frames, int img_h,
+                     int img_w, int H, int W, int32_t* frame_i, float* frame_minv, int32_t* clip_i, float* clip_f, void* stream);
+
 /* ---- mesh overlay on the device (csrc/render.hip; definitions in docs/design/11_render.md) ---------------------------------------------
  * The reference's lib/utils/renderer.py Renderer.render (pyrender on OpenGL) as a compute rasteriser: B meshes that share one face list are rotated by 180 degrees
  * about x (renderer.py:78-79), optionally rotated again (:84-86), projected by the weak-perspective camera (:31-38), z-buffered, shaded and written over uint8 frames.

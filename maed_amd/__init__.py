@@ -12,4 +12,5 @@ from .iterative import Regressor  # noqa: F401
 from .evaluate import Evaluator  # noqa: F401
 from .ops import set_float32_matmul_precision, get_float32_matmul_precision, set_float32_backward_precision, get_float32_backward_precision  # noqa: F401
 from .render import Renderer, FaceList, render_batch, render_people, render_frame_results, convert_crop_cam_to_orig_img, prepare_rendering_results  # noqa: F401
+from .video import VideoInference, track_boxes  # noqa: F401
 from ._lib import device_faults  # noqa: F401,E402

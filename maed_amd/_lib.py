@@ -201,6 +201,10 @@ SIGNATURES = {
     "maed_opt_step": (i32, [vp, vp, vp, vp, vp, i64, C.POINTER(OptArgs), vp]),
     "maed_clip_preprocess_workspace": (C.c_size_t, [i32, i32, i32]),
     "maed_clip_preprocess": (i32, [vp, i64, vp, vp, vp, vp, i32, i32, i32, i32, C.POINTER(f32), i32, i32, vp, vp, C.c_size_t, vp]),
+    "maed_track_boxes_workspace": (C.c_size_t, [i32, i32]),
+    "maed_track_boxes": (i32, [vp, vp, i32, i32, i32, C.c_double, i32, C.c_double, C.c_double, vp, vp, vp, vp, C.c_size_t, vp]),
+    "maed_track_smooth": (i32, [vp, vp, i32, i32, i32, C.c_double, C.c_double, vp, vp, vp, C.c_size_t, vp]),
+    "maed_crop_tables": (i32, [vp, i32, vp, vp, i32, i32, i32, i32, i32, i32, i32, vp, vp, vp, vp, vp]),
     "maed_render_mesh_workspace": (C.c_size_t, [i32, i32, i32, i32, i32, i32]),
     "maed_render_mesh": (i32, [vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, i32, i32, i32, i32, i32, C.POINTER(f32), f32, i32, vp, C.c_size_t, vp]),
     "maed_render_people_workspace": (C.c_size_t, [i32, i32, i32, i32, i32, i32, i32]),
